@@ -6,10 +6,13 @@
         bench.py --gpus N --steps K --warmup W
 
 One "step" = one iteration of train.py:48-221 (D phase, lazy R1 when iter % 16 == 0, G phase, Ex step, EMA)
-on a synthetic batch already resident in HBM.  Workload: BASELINE.json configs[2] — N=1, sigma=1, 256x256,
+on a synthetic batch already resident in HBM, every one from the same starting state (seeded initial networks; the optimiser and
+EMA state are restored before each iteration, see run_steps), with its own seeded draws.  Workload: BASELINE.json configs[2] — N=1, sigma=1, 256x256,
 batch 32 per GPU, full-width networks (channel 32, texture 2048), f32, through the HIP kernels of
 libideas_hip.so.  Weak scaling: every rank owns its own 32-image shard; gradients are averaged with one RCCL
-all-reduce per optimiser group (ideas_amd/ddp.py).  Rank 0 prints ONE JSON line.
+all-reduce per optimiser group (ideas_amd/ddp.py).  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the window
+and prints the line; --full adds the side measurements (rooflines, CPU baselines, extraction check, bf16 window, eager comparison);
+--dump-outputs DIR writes what the window's last step computed (capture_outputs).
 """
 import argparse
 import json
@@ -47,7 +50,7 @@ def flop_per_image(elided: bool, d_reg_every: int = 16, shared: bool = True) -> 
     return d_phase + g_fwd + g_bwd + second + r1
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=48, help="timed iterations (48 = three lazy-R1 iterations at d_reg_every 16)")
@@ -65,14 +68,26 @@ def parse():
     p.add_argument("--no-share-forward", action="store_true",
                    help="evaluate E(X) and G(S1,T1) in both phases like train.py:58,68,145,155 (same results, +4.6 %% FLOPs)")
     p.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam + per-tensor EMA instead of FusedAdamEMA")
-    p.add_argument("--cpu-baseline", choices=["auto", "skip"], default="auto")
-    p.add_argument("--roofline", choices=["on", "off", "only"], default="on")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline window: CPU baselines and the extraction check against the oracle, the "
+                        "rooflines and the per-family census, the lazy-R1 re-weighting, the bf16 window, the eager comparison.  "
+                        "Without it the run sets up, warms up, times --steps iterations and prints the line")
+    p.add_argument("--cpu-baseline", choices=["auto", "skip"], default=None, help="default: auto with --full, else skip")
+    p.add_argument("--roofline", choices=["on", "off", "only"], default=None, help="default: on with --full, else off")
     p.add_argument("--roofline-launches", type=int, default=20)
-    p.add_argument("--also-bf16", choices=["on", "off"], default="on",
-                   help="after the f32 window, time a short bf16 window in the same process and report it under \"bf16\"")
+    p.add_argument("--also-bf16", choices=["on", "off"], default=None,
+                   help="after the f32 window, time a short bf16 window in the same process and report it under \"bf16\" "
+                        "(default: on with --full, else off)")
     p.add_argument("--bf16-steps", type=int, default=16)
     p.add_argument("--bf16-warmup", type=int, default=4)
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed window, write what its last step computed to DIR/<name>.npy (float32): every entry of the "
+                        "losses dict train_iteration returned and a fixed seeded sample of every network's parameters")
+    a = p.parse_args(argv)
+    for k, on, off in (("cpu_baseline", "auto", "skip"), ("roofline", "on", "off"), ("also_bf16", "on", "off")):
+        if getattr(a, k) is None:
+            setattr(a, k, on if a.full else off)
+    return a
 
 
 def roofline_probe_bf16(device, batch: int, launches: int):
@@ -736,7 +751,9 @@ def main():
         print(json.dumps(rooflines(device, a.batch, a.roofline_launches, bf16)))
         return
 
-    res = run_steps(a, a.precision, a.steps, a.warmup, device, world, rank)
+    res = run_steps(a, a.precision, a.steps, a.warmup, device, world, rank, dump=a.dump_outputs is not None)
+    if a.dump_outputs is not None and rank == 0:
+        write_outputs(a.dump_outputs, res["outputs"])
     if rank != 0:
         if dist.is_initialized():
             dist.destroy_process_group()
@@ -755,7 +772,8 @@ def main():
         out["roofline_weighted"] = res["roofline_weighted"]
     if res.get("r1_reweighted"):
         out["r1_reweighted"] = res["r1_reweighted"]
-    out["vs_rocm_eager"] = leg("vs_rocm_eager", lambda: vs_rocm_eager(out["value"], a, world))
+    if a.full:
+        out["vs_rocm_eager"] = leg("vs_rocm_eager", lambda: vs_rocm_eager(out["value"], a, world))
     if a.roofline == "on":
         out.update(leg("rooflines", lambda: rooflines(device, a.batch, a.roofline_launches, bf16, errors)) or {})
     r2 = None
@@ -840,9 +858,10 @@ def _barrier(device):
         dist.barrier()
 
 
-def run_steps(a, precision_name, steps, warmup, device, world, rank):
+def run_steps(a, precision_name, steps, warmup, device, world, rank, dump=False):
     """Build the trainer in `precision_name`, run `warmup` untimed and exactly `steps` timed iterations between
-    barrier + synchronize pairs; returns the max-over-ranks wall time and what the line needs.  Frees everything on return."""
+    barrier + synchronize pairs; returns the max-over-ranks wall time and what the line needs (`dump`: on rank 0 also what the
+    last timed step computed, taken before anything else runs on the trainer).  Frees everything on return."""
     from ideas_amd import precision, train_step as TS
     from ideas_amd.models import init_model
     from ideas_amd.ddp import GradReducer
@@ -869,7 +888,13 @@ def run_steps(a, precision_name, steps, warmup, device, world, rank):
     dist_on = dist.is_initialized()           # world > 1, or the one-rank RCCL exercise of IDEAS_DDP_FORCE_COLLECTIVE=1
     reducer = GradReducer() if dist_on else None
 
+    # every iteration starts from the state the trainer has now: the adversarial step amplifies the run-to-run order of the kernels'
+    # atomic accumulations from one optimiser step to the next, so only a fixed starting state makes what a step computes the same
+    # in every run (to rounding).  The restore is a few device copies (~1.4 GB at full width), inside the timed window.
+    restore = state_restorer(trainer)
+
     def step(idx):
+        restore()
         return TS.train_iteration(trainer, args, X, idx, reducer=reducer)
 
     for j in range(warmup):
@@ -906,6 +931,7 @@ def run_steps(a, precision_name, steps, warmup, device, world, rank):
         if len(set(keys)) != len(keys) and os.environ.get("IDEAS_BENCH_SHARE_GPU") != "1":
             raise SystemExit(f"bench.py: {len(keys)} ranks on {len(set(keys))} distinct device(s) {keys}: every rank needs its own GPU "
                              "(LOCAL_RANK -> device index; check the launcher's device visibility)")
+    outputs = capture_outputs(trainer, losses) if (dump and rank == 0) else None
     # lazy-R1 weighting of the window: K timed steps hold floor(K / 16) R1 iterations, not K / 16 (20 steps: 1 in 20).  The extra cost of
     # an R1 iteration is measured right here (two R1 and two plain iterations, each between synchronisations) so that the line can
     # state the rate at exactly one R1 iteration in sixteen next to the measured one.
@@ -944,7 +970,7 @@ def run_steps(a, precision_name, steps, warmup, device, world, rank):
     res = {"dt": dt, "steps": steps, "warmup": warmup, "roofline_weighted": weighted, "r1_reweighted": r1w, "extraction": extraction,
            "n_r1": sum(1 for i in range(1, steps + 1) if i % args.d_reg_every == 0),
            "losses": {k: round(float(v.detach()), 4) for k, v in losses.items() if v.numel() == 1},
-           "ranks_seen": ranks_seen,
+           "ranks_seen": ranks_seen, "outputs": outputs,
            "bucket_bytes": ({k: 4 * int(trainer[k].flat_g.numel()) for k in ("d_optim", "g_optim", "ex_optim") if hasattr(trainer[k], "flat_g")}
                             if dist_on else None)}
     del trainer, reducer, losses, X
@@ -953,6 +979,69 @@ def run_steps(a, precision_name, steps, warmup, device, world, rank):
     torch.cuda.empty_cache()
     precision.set_activation_dtype("f32")
     return res
+
+
+def state_restorer(trainer):
+    """Saves what a training iteration updates, as it stands now, and returns a function that puts it back: the fused optimisers'
+    flat parameter / second-moment / EMA buffers and step counts (gradients are zeroed by the iteration itself); with --torch-adam
+    every network parameter, and the Adam state, which must still be empty (no step taken yet)."""
+    from ideas_amd.optim import FusedAdamEMA
+    opts = [v for v in trainer.values() if isinstance(v, torch.optim.Optimizer)]
+    fused = all(isinstance(o, FusedAdamEMA) for o in opts)
+    if fused:
+        live = [t for o in opts for t in (o.flat_p, o.flat_v, o.flat_ema) if t is not None]
+        steps = [list(o._pstep) for o in opts]
+    else:
+        if any(o.state for o in opts):
+            raise RuntimeError("state_restorer: an optimiser has already stepped")
+        live = [p.data for v in trainer.values() if isinstance(v, torch.nn.Module) for p in v.parameters()]
+    saved = [t.clone() for t in live]
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_(live, saved)
+        for i, o in enumerate(opts):
+            if fused:
+                o._pstep = list(steps[i])
+            else:
+                o.state.clear()
+    return restore
+
+
+DUMP_SAMPLE = 1 << 16          # parameters per network that --dump-outputs writes (a smaller network: all of them)
+
+
+def capture_outputs(trainer, losses):
+    """What one step computed, on the host as float32: every entry of train_iteration's losses dict (`loss_<name>`) and, per
+    network, DUMP_SAMPLE values at fixed seeded positions of the concatenation of its parameters in named_parameters order, each
+    parameter flattened in logical order whatever its memory format (`params_<net>`)."""
+    out = {"loss_" + k: v.detach().float().cpu().numpy() for k, v in losses.items()}
+    for name, net in trainer.items():
+        if not isinstance(net, torch.nn.Module):
+            continue
+        ps = [p.detach() for p in net.parameters()]
+        sizes = torch.tensor([p.numel() for p in ps], dtype=torch.int64)
+        ends = sizes.cumsum(0)
+        n = int(ends[-1])
+        if n <= DUMP_SAMPLE:
+            idx = torch.arange(n)
+        else:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(2024)).sort().values
+        which = torch.searchsorted(ends, idx, right=True)
+        vals = torch.empty(idx.numel(), dtype=torch.float32)
+        for j in which.unique().tolist():
+            m = which == j
+            local = idx[m] - (ends[j] - sizes[j])
+            vals[m] = ps[j].reshape(-1).index_select(0, local.to(ps[j].device)).float().cpu()
+        out["params_" + name] = vals.numpy()
+    return out
+
+
+def write_outputs(path, outputs):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def step_line(a, precision_name, res, world):

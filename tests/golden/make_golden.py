@@ -670,8 +670,7 @@ def gen_ckpt(RM, RU, RL, RO):
         # The reference's ImageLevelDiscriminator cannot be narrowed (models.py:336-341 hard-codes 512 channels below 64x64): 24 M
         # parameters = 96 MB of weights + 192 MB of Adam state in this checkpoint.  Its tensors above BIG elements (and the Adam state
         # of those parameters) are therefore NOT stored; what is stored for each of them is its shape, its f64 sum / abs-sum and 8
-        # seeded +-1 projections (`sketch`).  tests/test_host_logic.py loads the COMPLETE file, regenerated by this script, when
-        # /root/reference is present; the GPU test fills the omitted tensors from its own iteration 1 and checks them against these.
+        # seeded +-1 projections (`sketch`).  The GPU test fills the omitted tensors from its own iteration 1 and checks them against these.
         BIG = 1 << 16
         dreal_names = [n_ for n_, _ in trainer["Dreal"].named_parameters()]
         omitted = []
@@ -697,10 +696,6 @@ def gen_ckpt(RM, RU, RL, RO):
                 sums[name] = [float(sum(v.sum() for v in fl)), float(sum(v.abs().sum() for v in fl))]
         out["ck.omitted"] = np.array(json.dumps(omitted))
         out["ck.dreal_param_names"] = np.array(json.dumps(dreal_names))
-        full = os.environ.get("IDEAS_CKPT_COPY")          # tests/test_host_logic.py: keep the reference's own file for the complete check
-        if full:
-            import shutil
-            shutil.copy(path, full)
         out["ck.checksums"] = np.array(json.dumps(sums))
         print("checkpoint 1.pt:", {k: len(v) if hasattr(v, "__len__") else v for k, v in ck["trainer"].items()})
     gen_step(RM, RU, RL, RO, "ckpt", save_every=1, file_name="ckpt_r256.npz", extra=extra)
@@ -742,8 +737,43 @@ def gen_ops6(RM, RU, RL, RO):
     print("ops_r06.npz", len(out), "arrays")
 
 
+def gen_datasets():
+    """The reference's own dataset.py (LMDBDataset, NormalDataset) on the seeded LMDB store and image folder tests/test_data.py
+    builds, with its lmdb stand-in and a two-line imutils stub, given a transform that returns the PIL image's pixels: per case the
+    key / file order and the pixels of every item, for tests/test_data.py to hold ideas_amd.data's classes to."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    import lmdb_standin
+    import test_data as TD
+    paths = types.ModuleType("imutils.paths")
+    paths.list_files = lambda p: (os.path.join(r, f) for r, _, fs in os.walk(p) for f in fs)
+    imutils = types.ModuleType("imutils")
+    imutils.paths = paths
+    sys.modules.update({"lmdb": lmdb_standin, "imutils": imutils, "imutils.paths": paths})
+    sys.modules.pop("dataset", None)
+    sys.path.insert(0, REF)
+    import dataset as RD
+    to_u8 = lambda img: np.asarray(img.convert("RGB"), dtype=np.uint8).copy()
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        TD._lmdb_store(os.path.join(tmp, "db"), n=7)
+        for max_num in (70000, 2):
+            a = RD.LMDBDataset(os.path.join(tmp, "db"), to_u8, 48, max_num)
+            out[f"lmdb.{max_num}.keys"] = np.array(json.dumps([k.decode() for k in a.keys]))
+            out[f"lmdb.{max_num}.pixels"] = np.stack([a[i] for i in range(len(a))])
+        TD._make_images(os.path.join(tmp, "folder"))
+        a = RD.NormalDataset(os.path.join(tmp, "folder"), to_u8, 48)
+        out["folder.files"] = np.array(json.dumps([os.path.relpath(f, os.path.join(tmp, "folder")) for f in a.files]))
+        out["folder.pixels"] = np.stack([a[i] for i in range(len(a))])
+    np.savez_compressed(os.path.join(OUT, "datasets_ref.npz"), **out)
+    print("datasets_ref.npz", len(out), "arrays")
+
+
 if __name__ == "__main__":
     todo = sys.argv[1:] or ["ops", "nets", "init", "step_r64", "step_r256", "step_r64_N2", "step_r128", "step_r256_N2", "pathlen"]
+    if todo == ["datasets"]:            # the reference's dataset.py only: nothing of its model code is imported
+        gen_datasets()
+        sys.exit(0)
     mods = import_reference()
     torch.set_num_threads(8)
     if "ops" in todo:

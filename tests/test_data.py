@@ -84,35 +84,27 @@ def test_lmdb_dataset_executes_against_the_api_standin(tmp_path, monkeypatch):
     assert tuple(batch.shape) == (4, 32, 32, 3)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("IDEAS_REFERENCE", "/root/reference")), reason="needs the reference checkout (build container only)")
 def test_lmdb_and_folder_datasets_against_the_reference_classes(tmp_path, monkeypatch):
-    """The reference's OWN dataset.py (LMDBDataset and NormalDataset, dataset.py:10-73) imported in the build container with the lmdb
-    stand-in and a two-line imutils stub, given a transform that returns the PIL image's pixels: same length, same order, same pixels as
-    ideas_amd.data's classes on the same store / folder."""
+    """The reference's OWN dataset.py (LMDBDataset and NormalDataset, dataset.py:10-73), run with the lmdb stand-in and a two-line
+    imutils stub on this test's seeded store / folder and given a transform that returns the PIL image's pixels, left its key order,
+    file order and pixels in tests/golden/datasets_ref.npz (make_golden.py datasets): ideas_amd.data's classes on the same store /
+    folder give the same length, the same order and the same pixels."""
     import sys
-    import types
     import lmdb_standin
-    ref = os.environ.get("IDEAS_REFERENCE", "/root/reference")
-    paths = types.ModuleType("imutils.paths")
-    paths.list_files = lambda p: (os.path.join(r, f) for r, _, fs in os.walk(p) for f in fs)
-    imutils = types.ModuleType("imutils")
-    imutils.paths = paths
-    for name, mod in (("lmdb", lmdb_standin), ("imutils", imutils), ("imutils.paths", paths)):
-        monkeypatch.setitem(sys.modules, name, mod)
-    monkeypatch.syspath_prepend(ref)
-    monkeypatch.delitem(sys.modules, "dataset", raising=False)
-    import dataset as RD
-    to_u8 = lambda img: torch.from_numpy(np.asarray(img.convert("RGB"), dtype=np.uint8).copy())
+    from conftest import Golden
+    monkeypatch.setitem(sys.modules, "lmdb", lmdb_standin)
+    g = Golden("datasets_ref.npz")
     _lmdb_store(str(tmp_path / "db"), n=7)
     for max_num in (70000, 2):
-        a, b = RD.LMDBDataset(str(tmp_path / "db"), to_u8, 48, max_num), D.LMDBDataset(str(tmp_path / "db"), 48, max_num)
-        assert len(a) == len(b) and a.keys == b.keys
-        assert all(torch.equal(a[i], b[i]) for i in range(len(a)))
+        want = g.z[f"lmdb.{max_num}.pixels"]
+        b = D.LMDBDataset(str(tmp_path / "db"), 48, max_num)
+        assert len(want) == len(b) and [k.encode() for k in g.json(f"lmdb.{max_num}.keys")] == b.keys
+        assert all(np.array_equal(want[i], b[i].numpy()) for i in range(len(b)))
     _make_images(str(tmp_path / "folder"))
-    a, b = RD.NormalDataset(str(tmp_path / "folder"), to_u8, 48), D.NormalDataset(str(tmp_path / "folder"), 48)
-    assert len(a) == len(b) == 7 and [os.path.basename(f) for f in a.files] == [os.path.basename(f) for f in b.files]
-    assert all(torch.equal(a[i], b[i]) for i in range(len(a)))
-    monkeypatch.delitem(sys.modules, "dataset", raising=False)
+    want = g.z["folder.pixels"]
+    b = D.NormalDataset(str(tmp_path / "folder"), 48)
+    assert len(want) == len(b) == 7 and g.json("folder.files") == [os.path.relpath(f, str(tmp_path / "folder")) for f in b.files]
+    assert all(np.array_equal(want[i], b[i].numpy()) for i in range(len(b)))
 
 
 def test_shard_sampler_partitions_one_permutation():

@@ -229,7 +229,7 @@ def test_checkpoint_written_by_the_reference_loads_strictly(tmp_path):
     its first iteration (train.py:308-322; tiny width, 256x256, real Dco): rebuilt into the reference's dict, written with torch.save
     and read by ideas_amd.checkpoint.load with strict load_state_dict on all 11 networks and the 3 optimisers (train.py:435-442).
     (The 13 largest tensors of the reference's un-narrowable Dreal + their Adam state are not in the fixture: zeros here; the GPU test
-    fills them from its own first iteration, the test below reads the complete file when the reference is present.)"""
+    fills them from its own first iteration.)"""
     from conftest import Golden
     from ckpt_fixture import build_reference_checkpoint, omitted_entries
     from ideas_amd import checkpoint as CK
@@ -249,37 +249,6 @@ def test_checkpoint_written_by_the_reference_loads_strictly(tmp_path):
     for p in tr["G"].parameters():
         if p.dim() == 4:
             assert p.is_contiguous(memory_format=torch.channels_last)
-
-
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("IDEAS_REFERENCE", "/root/reference")), reason="needs the reference checkout (build container only)")
-def test_checkpoint_fixture_is_the_file_the_reference_writes(tmp_path):
-    """The reference's unmodified train() is run again (tests/golden/make_golden.py ckpt, ~40 s): (a) the regenerated fixture equals the
-    committed one array for array; (b) the COMPLETE file train() wrote -- the pickle itself, Dreal's 24 M parameters and their Adam
-    state included -- loads through ideas_amd.checkpoint.load with strict=True and every tensor arrives."""
-    import subprocess
-    import sys
-    import numpy as np
-    from ideas_amd import checkpoint as CK
-    copy = str(tmp_path / "ref_1.pt")
-    env = dict(os.environ, IDEAS_GOLDEN_OUT=str(tmp_path), IDEAS_CKPT_COPY=copy)
-    subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden.py"), "ckpt"], check=True, env=env, capture_output=True, timeout=600)
-    new, old = np.load(str(tmp_path / "ckpt_r256.npz")), np.load(os.path.join(GOLDEN, "ckpt_r256.npz"))
-    assert new.files == old.files
-    for k in old.files:
-        assert np.array_equal(new[k], old[k]), k
-    # the pickle holds the generator script's int-like channel_multiplier (make_golden.Shrink) under __main__
-    import __main__
-    sys.path.insert(0, GOLDEN)
-    import make_golden
-    __main__.Shrink = make_golden.Shrink
-    try:
-        raw = torch.load(copy, map_location="cpu", weights_only=False)
-        tr, _ = _ckpt_trainer(6)
-        assert CK.load(copy, tr) == 1
-    finally:
-        del __main__.Shrink
-    _assert_loaded(tr, raw)
-    assert sum(v.numel() for v in raw["trainer"]["Dreal"].values()) > 2e7
 
 
 def test_sample_sheet_layout_and_quantisation(tmp_path):
@@ -503,6 +472,57 @@ def test_bench_evidence_readers_drop_stale_files(tmp_path, monkeypatch):
     assert bench.eager_complete(a)["file"] == "profiles/r06_eager_full.json"
     (tmp_path / "oracle" / "torch_ref.py").write_text("the comparator's step changed")
     assert bench.eager_complete(a) is None
+
+
+def test_bench_plain_run_and_output_dump():
+    """A plain bench run measures its window only (every side measurement is behind --full, explicit switches still win), and
+    --dump-outputs writes the losses and a fixed, seeded, float32 parameter sample per network: the same on every call."""
+    import bench
+    import numpy as np
+    a = bench.parse([])
+    assert not a.full and (a.cpu_baseline, a.roofline, a.also_bf16, a.dump_outputs) == ("skip", "off", "off", None)
+    a = bench.parse(["--full"])
+    assert (a.cpu_baseline, a.roofline, a.also_bf16) == ("auto", "on", "on")
+    assert bench.parse(["--roofline", "only"]).roofline == "only" and bench.parse(["--full", "--cpu-baseline", "skip"]).cpu_baseline == "skip"
+    torch.manual_seed(0)
+    nets = {"big": torch.nn.Sequential(torch.nn.Conv2d(96, 96, 3), torch.nn.Linear(96, 16)), "small": torch.nn.Linear(3, 2), "opt": object()}
+    nets["big"][0].weight.data = nets["big"][0].weight.data.contiguous(memory_format=torch.channels_last)
+    losses = {"L": torch.tensor(1.5), "hat_Z": torch.randn(2, 1, 4, 4)}
+    out = bench.capture_outputs(nets, losses)
+    assert set(out) == {"loss_L", "loss_hat_Z", "params_big", "params_small"}
+    assert out["params_big"].shape == (bench.DUMP_SAMPLE,) and out["params_big"].dtype == np.float32
+    assert np.array_equal(out["params_small"], torch.cat([p.detach().reshape(-1) for p in nets["small"].parameters()]).numpy())
+    flat = torch.cat([p.detach().reshape(-1) for p in nets["big"].parameters()]).numpy()
+    assert np.isin(out["params_big"], flat).all()                   # values of the parameters, in logical order
+    again = bench.capture_outputs(nets, losses)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    assert np.array_equal(out["loss_hat_Z"], losses["hat_Z"].numpy())
+
+
+def test_bench_restores_the_starting_state_before_every_iteration():
+    """bench.py runs every iteration from the same starting state, so that what its timed path computes is the same in every run:
+    the restorer puts back every parameter (EMA copies included) and empties the Adam state (the --torch-adam form; the fused
+    optimisers' flat buffers need a GPU and are exercised by every bench run)."""
+    import bench
+    torch.manual_seed(1)
+    net, ema = torch.nn.Linear(5, 4), torch.nn.Linear(5, 4)
+    tr = {"G": net, "G_ema": ema, "g_optim": torch.optim.Adam(net.parameters(), lr=0.1)}
+    before = [p.detach().clone() for p in list(net.parameters()) + list(ema.parameters())]
+    restore = bench.state_restorer(tr)
+    for _ in range(2):
+        net(torch.randn(3, 5)).square().sum().backward()
+        tr["g_optim"].step()
+        with torch.no_grad():
+            for e, p in zip(ema.parameters(), net.parameters()):
+                e.lerp_(p, 0.5)
+        assert tr["g_optim"].state and not torch.equal(net.weight, before[0])
+        restore()
+        assert not tr["g_optim"].state
+        assert all(torch.equal(p, b) for p, b in zip(list(net.parameters()) + list(ema.parameters()), before))
+    with pytest.raises(RuntimeError):
+        net(torch.randn(3, 5)).sum().backward()
+        tr["g_optim"].step()
+        bench.state_restorer(tr)
 
 
 def test_conv_bias_call_sites_are_the_rgb_head_only():

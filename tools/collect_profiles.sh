@@ -26,7 +26,7 @@ EOF
 }
 run_one() {   # $1 = precision, $2 = tag, $3 = weight-gradient kernel source, $4.. = forward kernel source files
   P=$1; T=$2; WG=$3; shift 3
-  timeout 900 python $R/bench.py --precision $P > $OUT/${T}_bench_default.log 2>&1
+  timeout 900 python $R/bench.py --full --precision $P > $OUT/${T}_bench_default.log 2>&1
   tail -1 $OUT/${T}_bench_default.log > $OUT/${T}_bench_default.json
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${T}_roofline -- python $R/bench.py --precision $P --roofline only --also-bf16 off > $OUT/${T}_roofline.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${T}_step -- python $R/bench.py --precision $P --steps 3 --warmup 2 --cpu-baseline skip --roofline off --also-bf16 off > $OUT/${T}_step.log 2>&1

@@ -18,6 +18,8 @@ NCHW, NHWC = 0, 1
 F32 = 0
 F32_B3 = 1   # f32 tensors, split-bf16 contraction (IDEAS_F32_B3)
 BF16 = 2     # bf16 activations, bf16 MFMA with f32 accumulation, f32 master weights (IDEAS_BF16)
+F16 = 3      # half activations, f32 arithmetic (IDEAS_F16: ideas_fused_bias_act and ideas_upfirdn2d only)
+F64 = 4      # double activations and arithmetic (IDEAS_F64: ideas_fused_bias_act and ideas_upfirdn2d only)
 
 
 def act_dtype(t: torch.Tensor) -> int:
@@ -27,6 +29,18 @@ def act_dtype(t: torch.Tensor) -> int:
     if t.dtype == torch.bfloat16:
         return BF16
     raise RuntimeError(f"ideas_amd: only float32 and bfloat16 activations are implemented, got {t.dtype}")
+
+
+def op_dtype(t: torch.Tensor) -> int:
+    """dtype enum of the two drop-in ops (``ideas_fused_bias_act``, ``ideas_upfirdn2d``), which also take what the reference's
+    kernels dispatch beyond f32: half and double."""
+    if t.dtype == torch.float16:
+        return F16
+    if t.dtype == torch.float64:
+        return F64
+    if t.dtype == torch.float32 or t.dtype == torch.bfloat16:
+        return act_dtype(t)
+    raise RuntimeError(f"ideas_amd: fused_leaky_relu / upfirdn2d take float32, bfloat16, float16 and float64, got {t.dtype}")
 
 
 class ConvParams(C.Structure):

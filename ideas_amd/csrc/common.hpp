@@ -20,6 +20,11 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // Workgroup id -> tile id so that each XCD (block b runs on XCD b % 8, private 4 MiB L2) owns a contiguous band of tiles.
 // Bijective for any grid size (the q/rem form of cdna_hip_programming.md T1).
@@ -42,7 +47,7 @@ __device__ __forceinline__ void splitk_xcd_map(int L, int tiles, int splits, int
     tile = l - split * tiles;
 }
 
-// ---- activation element access for the two storage dtypes: f32 arithmetic either way --------------------------------
+// ---- activation element access for the storage dtypes: f32 arithmetic for f32 / bf16 / f16, f64 for f64 --------------------------------
 typedef unsigned short ideas_bf16;                 // one bf16 element in HBM
 struct ideas_bf16x4 { uint2 v; };                  // four consecutive bf16 (8 bytes)
 __device__ __forceinline__ unsigned ideas_pk_bf16(float a, float b) {          // two f32 -> two RNE bf16 (v_cvt_pk_bf16_f32)
@@ -65,8 +70,55 @@ template <> __device__ __forceinline__ ideas_bf16x4 from_f4<ideas_bf16x4>(float4
 }
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const ideas_bf16* p) { return __builtin_bit_cast(float, (unsigned)(*p) << 16); }
+__device__ __forceinline__ float ld1(const _Float16* p) { return (float)*p; }
+__device__ __forceinline__ double ld1(const double* p) { return *p; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(ideas_bf16* p, float v) { *p = (ideas_bf16)(ideas_pk_bf16(v, 0.f) & 0xffffu); }
+__device__ __forceinline__ void st1(_Float16* p, float v) { *p = (_Float16)v; }                  // one RNE rounding
+__device__ __forceinline__ void st1(double* p, double v) { *p = v; }
+
+// eight consecutive 2-byte elements (bf16 or f16) in one 16-byte vector <-> eight f32 (exact widening, RNE narrowing)
+__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8], ideas_bf16) {
+    f[0] = __builtin_bit_cast(float, u.x << 16); f[1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
+    f[2] = __builtin_bit_cast(float, u.y << 16); f[3] = __builtin_bit_cast(float, u.y & 0xffff0000u);
+    f[4] = __builtin_bit_cast(float, u.z << 16); f[5] = __builtin_bit_cast(float, u.z & 0xffff0000u);
+    f[6] = __builtin_bit_cast(float, u.w << 16); f[7] = __builtin_bit_cast(float, u.w & 0xffff0000u);
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8], ideas_bf16) {
+    return make_uint4(ideas_pk_bf16(f[0], f[1]), ideas_pk_bf16(f[2], f[3]), ideas_pk_bf16(f[4], f[5]), ideas_pk_bf16(f[6], f[7]));
+}
+typedef _Float16 ideas_f16x8_ __attribute__((ext_vector_type(8)));
+typedef float ideas_f32x8_ __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8], _Float16) {
+    const ideas_f32x8_ v = __builtin_convertvector(__builtin_bit_cast(ideas_f16x8_, u), ideas_f32x8_);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = v[e];
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8], _Float16) {
+    const ideas_f32x8_ v = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]};
+    return __builtin_bit_cast(uint4, __builtin_convertvector(v, ideas_f16x8_));
+}
+struct ideas_f16x8 { uint4 v; };                   // eight consecutive f16 (16 bytes)
+
+// a 16-byte (f32, f16) or 8-byte (bf16) activation vector as H float4: load / store with one rounding per element
+template <typename V> struct vec_io {
+    static constexpr int H = 1;
+    static __device__ __forceinline__ void load(const V& p, float4 (&o)[1]) { o[0] = to_f4(p); }
+    static __device__ __forceinline__ V store(const float4 (&o)[1]) { return from_f4<V>(o[0]); }
+};
+template <> struct vec_io<ideas_f16x8> {
+    static constexpr int H = 2;
+    static __device__ __forceinline__ void load(const ideas_f16x8& p, float4 (&o)[2]) {
+        float f[8];
+        unpack8(p.v, f, _Float16{});
+        o[0] = make_float4(f[0], f[1], f[2], f[3]);
+        o[1] = make_float4(f[4], f[5], f[6], f[7]);
+    }
+    static __device__ __forceinline__ ideas_f16x8 store(const float4 (&o)[2]) {
+        const float f[8] = {o[0].x, o[0].y, o[0].z, o[0].w, o[1].x, o[1].y, o[1].z, o[1].w};
+        return ideas_f16x8{pack8(f, _Float16{})};
+    }
+};
 
 // mirror an out-of-range coordinate back into [0,n) (ReflectionPad2d semantics, no edge repeat)
 __device__ __forceinline__ int reflect_coord(int i, int n) {

@@ -7,7 +7,7 @@
 //                   column and marches down the rows with a 4x4 register window: 4 x 16-byte loads and one
 //                   16-byte store per output, every access coalesced along C, no LDS needed.
 //   * blur_nchw_tile — NCHW (the reference's layout): LDS-staged (TH+kh-1) x (TW+kw-1) input tile per plane.
-//   * generic     — any up/down/kernel <= 8x8, either layout, one output per thread (the op's full contract).
+//   * generic     — any up/down/FIR size, either layout, any dtype, one output per thread (the op's full contract).
 #include "common.hpp"
 
 namespace {
@@ -21,16 +21,24 @@ struct FirParams {
 };
 
 // ---------------- generic: out[oy,ox] = sum_k U[oy*down + ky - pad0] * Kf[ky] ----------------------
-template <bool NHWC, typename T>
+// Any up / down / FIR size, either layout, one output per thread.  A = accumulation type and K = the FIR's element type: f32 for
+// f32 / bf16 / f16 tensors, f64 for f64.  With `lds_taps` (the host's choice: the table fits GENERIC_TAP_LDS bytes) the flipped,
+// gain-scaled taps are staged in LDS; otherwise every tap is formed from the FIR in global memory where it is used (the
+// reference's upfirdn2d_kernel_large covers any size as well).  Either way a tap's value is fir[src] * gain, so the two agree.
+#define GENERIC_TAP_LDS 32768
+template <bool NHWC, typename T, typename A, typename K>
 __global__ __launch_bounds__(256) void upfirdn2d_generic(T* __restrict__ y, const T* __restrict__ x,
-                                                         const float* __restrict__ fir, FirParams p) {
-    __shared__ float sk[64];
-    for (int t = threadIdx.x; t < p.kh * p.kw; t += blockDim.x) {
-        int ky = t / p.kw, kx = t % p.kw;
-        int src = p.flip ? (p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx) : t;
-        sk[t] = fir[src] * p.gain;
+                                                         const K* __restrict__ fir, FirParams p, int lds_taps) {
+    extern __shared__ double s_taps[];
+    A* sk = reinterpret_cast<A*>(s_taps);
+    if (lds_taps) {
+        for (int t = threadIdx.x; t < p.kh * p.kw; t += blockDim.x) {
+            int ky = t / p.kw, kx = t % p.kw;
+            int src = p.flip ? (p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx) : t;
+            sk[t] = (A)fir[src] * (A)p.gain;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     const int64_t total = (int64_t)p.B * p.C * p.out_h * p.out_w;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -45,7 +53,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_generic(T* __restrict__ y, cons
             oy = (int)(r % p.out_h); r /= p.out_h;
             c = (int)(r % p.C); b = (int)(r / p.C);
         }
-        float acc = 0.f;
+        A acc = 0;
         for (int ky = 0; ky < p.kh; ++ky) {
             int uy = oy * p.down_y + ky - p.pad_y0;
             if (uy < 0 || uy % p.up_y) continue;
@@ -58,7 +66,9 @@ __global__ __launch_bounds__(256) void upfirdn2d_generic(T* __restrict__ y, cons
                 if (ix >= p.in_w) continue;
                 int64_t src = NHWC ? (((int64_t)b * p.in_h + iy) * p.in_w + ix) * p.C + c
                                    : (((int64_t)b * p.C + c) * p.in_h + iy) * p.in_w + ix;
-                acc += ld1(x + src) * sk[ky * p.kw + kx];
+                const A k = lds_taps ? sk[ky * p.kw + kx]
+                                     : (A)fir[p.flip ? (p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx) : ky * p.kw + kx] * (A)p.gain;
+                acc += ld1(x + src) * k;
             }
         }
         st1(y + i, acc);
@@ -515,24 +525,16 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
     }
 }
 
-// ---------------- bf16 NHWC 4x4 blur, 8 channels (16 bytes) per thread -------------------------------------------------
+// ---------------- bf16 / f16 NHWC 4x4 blur, 8 channels (16 bytes) per thread ------------------------------------------
+// (E = ideas_bf16 or _Float16: the element type of the 16-byte vectors; arithmetic is f32 for both, see unpack8 / pack8)
 // With 2-byte elements the 4-channel window kernel above moves half the bytes per instruction and is latency-bound
 // (1.45 TB/s measured).  Here a thread owns 8 channels of one output column.  A 4x4 window of 8-channel inputs would be 128
 // registers, so the kernel uses that every FIR on the path is an outer product kv (x) kh (make_kernel, stylegan2/model.py:22-30):
 // each input row is reduced to ONE horizontally filtered row of 8 floats as it arrives, and the window is four of those.
 // The factorisation is checked on the device from the 16 taps; a FIR that is not rank 1 takes the direct 16-tap loop.
 struct F8 { float v[8]; };
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-    f[0] = __builtin_bit_cast(float, u.x << 16); f[1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
-    f[2] = __builtin_bit_cast(float, u.y << 16); f[3] = __builtin_bit_cast(float, u.y & 0xffff0000u);
-    f[4] = __builtin_bit_cast(float, u.z << 16); f[5] = __builtin_bit_cast(float, u.z & 0xffff0000u);
-    f[6] = __builtin_bit_cast(float, u.w << 16); f[7] = __builtin_bit_cast(float, u.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    return make_uint4(ideas_pk_bf16(f[0], f[1]), ideas_pk_bf16(f[2], f[3]), ideas_pk_bf16(f[4], f[5]), ideas_pk_bf16(f[6], f[7]));
-}
 
-template <int EPI>
+template <int EPI, typename E>
 __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x,
                                                     const float* __restrict__ fir, FirParams p, FirEpi ep) {
     __shared__ float sk[16];
@@ -578,12 +580,12 @@ __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const
     // the fused stage of one output vector (the blur is rounded to bf16 first, as the unfused blur -> bias_act path stores it)
     auto finish = [&](int oy, float (&o)[8]) {
         if (EPI != EPI_NONE) {
-            const uint4 q = pack8(o);
-            unpack8(q, o);
+            const uint4 q = pack8(o, E{});
+            unpack8(q, o, E{});
         }
         if (EPI == EPI_ACT_BWD) {
             float rf[8];
-            unpack8(rb[(int64_t)oy * p.out_w * C8], rf);
+            unpack8(rb[(int64_t)oy * p.out_w * C8], rf, E{});
 #pragma unroll
             for (int e = 0; e < 8; ++e) { o[e] = epi_act(o[e], rf[e], ep.alpha, ep.scale); bsum[e] += o[e]; }
             if (!active) return;
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float v = o[e] + bb[e]; o[e] = epi_act(v, v, ep.alpha, ep.scale); }
         }
-        yb[(int64_t)oy * p.out_w * C8] = pack8(o);
+        yb[(int64_t)oy * p.out_w * C8] = pack8(o, E{});
     };
     unsigned colmask = 0;
 #pragma unroll
@@ -622,7 +624,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     float f[8];
-                    unpack8(row[t], f);
+                    unpack8(row[t], f, E{});
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
                 }
@@ -638,7 +640,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             float f[8];
-            unpack8(row[t], f);
+            unpack8(row[t], f, E{});
 #pragma unroll
             for (int e = 0; e < 8; ++e) h.v[e] = fmaf(f[e], kh[t], h.v[e]);
         }
@@ -680,7 +682,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const
 // blur4_bf16x8 issues four 16-byte loads per 16-byte output; a thread that owns the column pair (2q, 2q+1) needs five per row for
 // two outputs (the windows overlap in three columns), i.e. 2.5 loads per output, and keeps two horizontally filtered values per
 // row.  Only for separable FIRs (every FIR of the path; others stay on the one-column kernel).
-template <int EPI>
+template <int EPI, typename E>
 __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, const uint4* __restrict__ x,
                                                        const float* __restrict__ fir, FirParams p, FirEpi ep) {
     __shared__ float sk[16];
@@ -728,12 +730,12 @@ __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, co
     auto finish = [&](int oy, int col, float (&o)[8]) {
         const int64_t off = (int64_t)oy * p.out_w * C8 + (int64_t)col * C8;
         if (EPI != EPI_NONE) {
-            const uint4 qv = pack8(o);
-            unpack8(qv, o);
+            const uint4 qv = pack8(o, E{});
+            unpack8(qv, o, E{});
         }
         if (EPI == EPI_ACT_BWD) {
             float rf[8];
-            unpack8(rb[off], rf);
+            unpack8(rb[off], rf, E{});
 #pragma unroll
             for (int e = 0; e < 8; ++e) { o[e] = epi_act(o[e], rf[e], ep.alpha, ep.scale); bsum[e] += o[e]; }
             if (!active) return;
@@ -742,7 +744,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, co
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float v = o[e] + bb[e]; o[e] = epi_act(v, v, ep.alpha, ep.scale); }
         }
-        yb[off] = pack8(o);
+        yb[off] = pack8(o, E{});
     };
     unsigned colmask = 0;
 #pragma unroll
@@ -762,7 +764,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, co
                         const int ix = ix0 + col + t;
                         if (ix < 0 || ix >= p.in_w) continue;
                         float f[8];
-                        unpack8(xb[((int64_t)iy * p.in_w + ix) * C8], f);
+                        unpack8(xb[((int64_t)iy * p.in_w + ix) * C8], f, E{});
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
                     }
@@ -789,7 +791,7 @@ __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, co
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
             float f[8];
-            unpack8(v[t], f);
+            unpack8(v[t], f, E{});
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 if (t < 4) ha.v[e] = fmaf(f[e], kh[t], ha.v[e]);
@@ -829,11 +831,12 @@ __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, co
     if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, 8 * c8, bsum, 8);
 }
 
-// ---------------- bf16 NHWC decimating / zero-stuffing 4x4 FIRs, 8 channels (16 bytes) per thread ------------------------------
+// ---------------- bf16 / f16 NHWC decimating / zero-stuffing 4x4 FIRs, 8 channels (16 bytes) per thread ------------------------
 // Same reason as blur4_bf16x8: with 2-byte elements the 4-channel kernels above move 8 bytes per lane and instruction and are
 // latency-bound (fir4_up2 / fir4_down2 on bf16: ~1.5 TB/s).  down2 keeps a window of four horizontally filtered rows (the FIR is an
 // outer product; checked on the device, a rank > 1 table takes the direct loop) and advances two input rows per output row; up2
 // keeps the 3 x 3 input neighbourhood of a 2 x 2 output block in registers (72 floats).
+template <typename E>
 __global__ __launch_bounds__(256) void fir4_down2_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x,
                                                          const float* __restrict__ fir, FirParams p) {
     __shared__ float sk[16];
@@ -891,12 +894,12 @@ __global__ __launch_bounds__(256) void fir4_down2_bf16x8(uint4* __restrict__ y, 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     float f[8];
-                    unpack8(row[t], f);
+                    unpack8(row[t], f, E{});
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
                 }
             }
-            yb[(int64_t)oy * p.out_w * C8] = pack8(acc);
+            yb[(int64_t)oy * p.out_w * C8] = pack8(acc, E{});
         }
         return;
     }
@@ -906,7 +909,7 @@ __global__ __launch_bounds__(256) void fir4_down2_bf16x8(uint4* __restrict__ y, 
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             float f[8];
-            unpack8(row[t], f);
+            unpack8(row[t], f, E{});
 #pragma unroll
             for (int e = 0; e < 8; ++e) h.v[e] = fmaf(f[e], kh[t], h.v[e]);
         }
@@ -927,11 +930,12 @@ __global__ __launch_bounds__(256) void fir4_down2_bf16x8(uint4* __restrict__ y, 
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = h0.v[e] * kv[0] + h1.v[e] * kv[1] + h2.v[e] * kv[2] + h3.v[e] * kv[3];
-        yb[(int64_t)oy * p.out_w * C8] = pack8(o);
+        yb[(int64_t)oy * p.out_w * C8] = pack8(o, E{});
         h0 = h2; h1 = h3;
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x, const float* __restrict__ fir,
                                                        FirParams p, const uint4* __restrict__ resid) {
     __shared__ float sk[16];
@@ -980,7 +984,7 @@ __global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, co
             const bool ok = rowok && ((colmask >> t) & 1u);
             const uint4 v = xr[(int64_t)(ok ? cx0 + t : 0) * C8];
             const unsigned m = ok ? 0xffffffffu : 0u;
-            unpack8(make_uint4(v.x & m, v.y & m, v.z & m, v.w & m), dst[t].v);
+            unpack8(make_uint4(v.x & m, v.y & m, v.z & m, v.w & m), dst[t].v, E{});
         }
     };
     F8 R0[3], R1[3], R2[3];
@@ -1010,14 +1014,14 @@ __global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, co
                 }
                 const int64_t yi = (((int64_t)b * p.out_h + oy) * p.out_w + 2 * j + bb) * C8 + c8;
                 if (resid) {
-                    const uint4 q = pack8(o);          // the two-kernel chain stores the FIR (bf16) first
-                    unpack8(q, o);
+                    const uint4 q = pack8(o, E{});          // the two-kernel chain stores the FIR (bf16) first
+                    unpack8(q, o, E{});
                     float rf[8];
-                    unpack8(resid[yi], rf);
+                    unpack8(resid[yi], rf, E{});
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] += rf[e];
                 }
-                y[yi] = pack8(o);
+                y[yi] = pack8(o, E{});
             }
         }
 #pragma unroll
@@ -1028,7 +1032,9 @@ __global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, co
 // ---------------- NCHW tiled blur, up = down = 1, k <= 4 -------------------------------------------
 #define TNH 16
 #define TNW 64
-__global__ __launch_bounds__(256) void blur_nchw_tile(float* __restrict__ y, const float* __restrict__ x,
+// T = float or _Float16 (the reference's half layout); the tile and the arithmetic are f32 for both
+template <typename T>
+__global__ __launch_bounds__(256) void blur_nchw_tile(T* __restrict__ y, const T* __restrict__ x,
                                                       const float* __restrict__ fir, FirParams p) {
     __shared__ float sk[16];
     __shared__ float sx[TNH + 3][TNW + 3 + 1];
@@ -1049,16 +1055,16 @@ __global__ __launch_bounds__(256) void blur_nchw_tile(float* __restrict__ y, con
     const int ty = (int)(bid % tiles_y);
     const int64_t plane = bid / tiles_y;
     const int oy0 = ty * TNH, ox0 = tx * TNW;
-    const float* xp = x + plane * p.in_h * p.in_w;
+    const T* xp = x + plane * p.in_h * p.in_w;
     for (int t = threadIdx.x; t < (TNH + 3) * (TNW + 3); t += blockDim.x) {
         int ry = t / (TNW + 3), rx = t % (TNW + 3);
         int iy = oy0 + ry - p.pad_y0, ix = ox0 + rx - p.pad_x0;
         float v = 0.f;
-        if (iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w) v = xp[(int64_t)iy * p.in_w + ix];
+        if (iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w) v = ld1(xp + (int64_t)iy * p.in_w + ix);
         sx[ry][rx] = v;
     }
     __syncthreads();
-    float* yp = y + plane * p.out_h * p.out_w;
+    T* yp = y + plane * p.out_h * p.out_w;
     for (int t = threadIdx.x; t < TNH * TNW; t += blockDim.x) {
         int ry = t / TNW, rx = t % TNW;
         int oy = oy0 + ry, ox = ox0 + rx;
@@ -1068,7 +1074,7 @@ __global__ __launch_bounds__(256) void blur_nchw_tile(float* __restrict__ y, con
         for (int ky = 0; ky < 4; ++ky)
 #pragma unroll
             for (int kx = 0; kx < 4; ++kx) acc += sx[ry + ky][rx + kx] * sk[ky * 4 + kx];
-        yp[(int64_t)oy * p.out_w + ox] = acc;
+        st1(yp + (int64_t)oy * p.out_w + ox, acc);
     }
 }
 
@@ -1088,15 +1094,23 @@ static int launch_blur4(void* y, const void* x, const float* fir, FirParams p, F
 #ifndef IDEAS_BLUR_C2
 #define IDEAS_BLUR_C2 1
 #endif
+    if constexpr (EPI == EPI_NONE) {          // f16 (C % 8 == 0, plain blur only): the 8-channel two-column kernel of bf16
+        if (dtype == IDEAS_F16) {
+            const int64_t total8 = (int64_t)p.B * segs * ((p.out_w + 1) / 2) * (p.C / 8);
+            hipLaunchKernelGGL((blur4_bf16x8_c2<EPI, _Float16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream,
+                               (uint4*)y, (const uint4*)x, fir, p, ep);
+            return ideas_launch_status();
+        }
+    }
     if (IDEAS_BLUR_C2 && dtype == IDEAS_BF16 && p.C % 8 == 0) {
         const int64_t total8 = (int64_t)p.B * segs * ((p.out_w + 1) / 2) * (p.C / 8);
-        hipLaunchKernelGGL(blur4_bf16x8_c2<EPI>, dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
+        hipLaunchKernelGGL((blur4_bf16x8_c2<EPI, ideas_bf16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
                            (const uint4*)x, fir, p, ep);
         return ideas_launch_status();
     }
     if (dtype == IDEAS_BF16 && p.C % 8 == 0) {
         const int64_t total8 = (int64_t)p.B * segs * p.out_w * (p.C / 8);
-        hipLaunchKernelGGL(blur4_bf16x8<EPI>, dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
+        hipLaunchKernelGGL((blur4_bf16x8<EPI, ideas_bf16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
                            (const uint4*)x, fir, p, ep);
     } else if (dtype == IDEAS_BF16)
         hipLaunchKernelGGL((blur4_nhwc<ideas_bf16x4, EPI>), dim3((unsigned)grid), dim3(256), lds, stream, (ideas_bf16x4*)y,
@@ -1138,28 +1152,33 @@ extern "C" int ideas_blur_fused(void* y, const void* x, const float* fir, int B,
 static int upfirdn2d_impl(void* y, const void* x, const float* fir, int B, int C, int in_h, int in_w, int out_h,
                           int out_w, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0,
                           int pad_y0, float gain, int flip, int layout, int dtype, void* stream_, const void* resid) {
-    if (dtype != IDEAS_F32 && dtype != IDEAS_BF16) return IDEAS_E_UNSUPPORTED;
+    if (dtype != IDEAS_F32 && dtype != IDEAS_BF16 && dtype != IDEAS_F16 && dtype != IDEAS_F64) return IDEAS_E_UNSUPPORTED;
     if (dtype == IDEAS_BF16 && layout != IDEAS_NHWC) return IDEAS_E_UNSUPPORTED;
     if (!y || !x || !fir) return IDEAS_E_NULL;
     if (B <= 0 || C <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return IDEAS_E_SHAPE;
-    if (kh <= 0 || kw <= 0 || kh > 8 || kw > 8) return IDEAS_E_UNSUPPORTED;
+    if (kh <= 0 || kw <= 0) return IDEAS_E_UNSUPPORTED;
     if (up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0) return IDEAS_E_SHAPE;
     if (layout != IDEAS_NCHW && layout != IDEAS_NHWC) return IDEAS_E_UNSUPPORTED;
     hipStream_t stream = (hipStream_t)stream_;
     FirParams p{B, C, in_h, in_w, out_h, out_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_y0, gain, flip, 16};
     const bool unit = up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1;
-    if (unit && layout == IDEAS_NHWC && kh == 4 && kw == 4 && (C % 4 == 0) && ideas_aligned16(x) && ideas_aligned16(y)) {
+    // the 4x4 NHWC kernels: f32 / bf16 at C % 4 == 0, f16 at C % 8 == 0 (8 channels per thread only); f64 has none
+    const bool fast = dtype == IDEAS_F32 || dtype == IDEAS_BF16 || (dtype == IDEAS_F16 && C % 8 == 0);
+    const bool vec4 = fast && layout == IDEAS_NHWC && kh == 4 && kw == 4 && (C % 4 == 0) && ideas_aligned16(x) && ideas_aligned16(y);
+    const bool x8 = (dtype == IDEAS_BF16 || dtype == IDEAS_F16) && C % 8 == 0;
+    if (unit && vec4) {
         return launch_blur4<EPI_NONE>(y, x, fir, p, FirEpi{nullptr, nullptr, nullptr, 0.f, 1.f}, dtype, stream);
     }
-    const bool vec4 = layout == IDEAS_NHWC && kh == 4 && kw == 4 && (C % 4 == 0) && ideas_aligned16(x) && ideas_aligned16(y);
     if (vec4 && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2) {
         p.seg_rows = out_h >= 64 ? 16 : 8;
         const int segs = (out_h + p.seg_rows - 1) / p.seg_rows;
         const int64_t grid = ideas_cdiv((int64_t)B * segs * out_w * (C / 4), 256);
         if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
-        if (dtype == IDEAS_BF16 && C % 8 == 0)
-            hipLaunchKernelGGL(fir4_down2_bf16x8, dim3((unsigned)ideas_cdiv((int64_t)B * segs * out_w * (C / 8), 256)), dim3(256), 0, stream,
-                               (uint4*)y, (const uint4*)x, fir, p);
+        const unsigned grid8 = (unsigned)ideas_cdiv((int64_t)B * segs * out_w * (C / 8), 256);
+        if (x8 && dtype == IDEAS_F16)
+            hipLaunchKernelGGL(fir4_down2_bf16x8<_Float16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
+        else if (x8)
+            hipLaunchKernelGGL(fir4_down2_bf16x8<ideas_bf16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
         else if (dtype == IDEAS_BF16)
             hipLaunchKernelGGL(fir4_down2_nhwc<ideas_bf16x4>, dim3((unsigned)grid), dim3(256), 0, stream, (ideas_bf16x4*)y,
                                (const ideas_bf16x4*)x, fir, p);
@@ -1174,9 +1193,13 @@ static int upfirdn2d_impl(void* y, const void* x, const float* fir, int B, int C
         const int segs = (bh + p.seg_rows - 1) / p.seg_rows;
         const int64_t grid = ideas_cdiv((int64_t)B * segs * bw * (C / 4), 256);
         if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
-        if (dtype == IDEAS_BF16 && C % 8 == 0)
-            hipLaunchKernelGGL(fir4_up2_bf16x8, dim3((unsigned)ideas_cdiv((int64_t)B * segs * bw * (C / 8), 256)), dim3(256), 0, stream,
-                               (uint4*)y, (const uint4*)x, fir, p, (const uint4*)resid);
+        const unsigned grid8 = (unsigned)ideas_cdiv((int64_t)B * segs * bw * (C / 8), 256);
+        if (x8 && dtype == IDEAS_F16)
+            hipLaunchKernelGGL(fir4_up2_bf16x8<_Float16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p,
+                               (const uint4*)resid);
+        else if (x8)
+            hipLaunchKernelGGL(fir4_up2_bf16x8<ideas_bf16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p,
+                               (const uint4*)resid);
         else if (dtype == IDEAS_BF16)
             hipLaunchKernelGGL(fir4_up2_nhwc<ideas_bf16x4>, dim3((unsigned)grid), dim3(256), 0, stream, (ideas_bf16x4*)y,
                                (const ideas_bf16x4*)x, fir, p, (const ideas_bf16x4*)resid);
@@ -1185,24 +1208,44 @@ static int upfirdn2d_impl(void* y, const void* x, const float* fir, int B, int C
                                (const float4*)resid);
         return ideas_launch_status();
     }
-    if (unit && layout == IDEAS_NCHW && kh <= 4 && kw <= 4) {
+    if (unit && layout == IDEAS_NCHW && kh <= 4 && kw <= 4 && (dtype == IDEAS_F32 || dtype == IDEAS_F16)) {
         const int64_t grid = (int64_t)B * C * ideas_cdiv(out_h, TNH) * ideas_cdiv(out_w, TNW);
         if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
-        hipLaunchKernelGGL(blur_nchw_tile, dim3((unsigned)grid), dim3(256), 0, stream, (float*)y, (const float*)x, fir, p);
+        if (dtype == IDEAS_F16)
+            hipLaunchKernelGGL(blur_nchw_tile<_Float16>, dim3((unsigned)grid), dim3(256), 0, stream, (_Float16*)y, (const _Float16*)x, fir, p);
+        else
+            hipLaunchKernelGGL(blur_nchw_tile<float>, dim3((unsigned)grid), dim3(256), 0, stream, (float*)y, (const float*)x, fir, p);
         return ideas_launch_status();
     }
     const int64_t total = (int64_t)B * C * out_h * out_w;
     int64_t grid = ideas_cdiv(total, 256);
     if (grid > 65536) grid = 65536;
+    const int64_t tap_bytes = (int64_t)kh * kw * (dtype == IDEAS_F64 ? sizeof(double) : sizeof(float));
+    const int lds_taps = tap_bytes <= GENERIC_TAP_LDS;
+    const size_t lds = lds_taps ? (size_t)tap_bytes : 0;
+    const dim3 g((unsigned)grid), blk(256);
+    const bool nhwc = layout == IDEAS_NHWC;
     if (dtype == IDEAS_BF16)
-        hipLaunchKernelGGL((upfirdn2d_generic<true, ideas_bf16>), dim3((unsigned)grid), dim3(256), 0, stream, (ideas_bf16*)y,
-                           (const ideas_bf16*)x, fir, p);
-    else if (layout == IDEAS_NHWC)
-        hipLaunchKernelGGL((upfirdn2d_generic<true, float>), dim3((unsigned)grid), dim3(256), 0, stream, (float*)y,
-                           (const float*)x, fir, p);
+        hipLaunchKernelGGL((upfirdn2d_generic<true, ideas_bf16, float, float>), g, blk, lds, stream, (ideas_bf16*)y,
+                           (const ideas_bf16*)x, fir, p, lds_taps);
+    else if (dtype == IDEAS_F16 && nhwc)
+        hipLaunchKernelGGL((upfirdn2d_generic<true, _Float16, float, float>), g, blk, lds, stream, (_Float16*)y, (const _Float16*)x,
+                           fir, p, lds_taps);
+    else if (dtype == IDEAS_F16)
+        hipLaunchKernelGGL((upfirdn2d_generic<false, _Float16, float, float>), g, blk, lds, stream, (_Float16*)y, (const _Float16*)x,
+                           fir, p, lds_taps);
+    else if (dtype == IDEAS_F64 && nhwc)          // f64: `fir` points to double (include/ideas_hip.h)
+        hipLaunchKernelGGL((upfirdn2d_generic<true, double, double, double>), g, blk, lds, stream, (double*)y, (const double*)x,
+                           (const double*)fir, p, lds_taps);
+    else if (dtype == IDEAS_F64)
+        hipLaunchKernelGGL((upfirdn2d_generic<false, double, double, double>), g, blk, lds, stream, (double*)y, (const double*)x,
+                           (const double*)fir, p, lds_taps);
+    else if (nhwc)
+        hipLaunchKernelGGL((upfirdn2d_generic<true, float, float, float>), g, blk, lds, stream, (float*)y, (const float*)x, fir, p,
+                           lds_taps);
     else
-        hipLaunchKernelGGL((upfirdn2d_generic<false, float>), dim3((unsigned)grid), dim3(256), 0, stream, (float*)y,
-                           (const float*)x, fir, p);
+        hipLaunchKernelGGL((upfirdn2d_generic<false, float, float, float>), g, blk, lds, stream, (float*)y, (const float*)x, fir, p,
+                           lds_taps);
     return ideas_launch_status();
 }
 
@@ -1216,6 +1259,7 @@ extern "C" int ideas_upfirdn2d(void* y, const void* x, const float* fir, int B, 
 extern "C" int ideas_fir_up2_add(void* y, const void* x, const float* fir, const void* resid, int B, int C, int in_h, int in_w,
                                  int out_h, int out_w, int pad_x0, int pad_y0, float gain, int flip, int dtype, void* stream_) {
     if (!resid) return IDEAS_E_NULL;
+    if (dtype != IDEAS_F32 && dtype != IDEAS_BF16) return IDEAS_E_UNSUPPORTED;       // (f16 / f64: ideas_upfirdn2d, then an add)
     return upfirdn2d_impl(y, x, fir, B, C, in_h, in_w, out_h, out_w, 4, 4, 2, 2, 1, 1, pad_x0, pad_y0, gain, flip, IDEAS_NHWC, dtype,
                           stream_, resid);
 }

@@ -44,9 +44,11 @@ def bias_act_raw(x: torch.Tensor, bias: Optional[torch.Tensor], ref: Optional[to
                  bias_grad_into: Optional[torch.Tensor] = None):
     """One launch of ``ideas_fused_bias_act``; returns ``y`` or ``(y, bias_grad)``.  ``bias_grad_into`` (a contiguous f32 [C]
     tensor, e.g. the bias parameter's ``.grad`` view of the flat bucket): the kernel ADDS the bias gradient to it instead of
-    filling a fresh zeroed buffer (no allocation, no fill, no later accumulate pass); the second return value is then None."""
+    filling a fresh zeroed buffer (no allocation, no fill, no later accumulate pass); the second return value is then None.
+    f16 / f64 tensors: the bias and its gradient are f32 for f16 and f64 for f64 (the kernel's side-argument types); the returned
+    bias gradient is cast to the bias's own dtype."""
     _lib.require_cuda(x, bias, ref)
-    dt = _lib.act_dtype(x)
+    dt = _lib.op_dtype(x)
     lib = _lib.load()
     if ref is not None:
         if ref.shape != x.shape:
@@ -67,15 +69,20 @@ def bias_act_raw(x: torch.Tensor, bias: Optional[torch.Tensor], ref: Optional[to
         else:
             y32 = bias_act_raw(x.float(), bias, None if ref is None else ref.float(), grad, alpha, scale, want_bias_grad, act)
             return (y32[0].to(x.dtype), y32[1]) if want_bias_grad else y32.to(x.dtype)
+    side = torch.float64 if dt == _lib.F64 else torch.float32        # bias / bias-gradient type of the kernel
+    bias_dtype = None
     if bias is not None:
         if bias.numel() != c:
             raise RuntimeError(f"fused_bias_act: bias has {bias.numel()} elements, expected {c}")
-        bias = bias.contiguous().to(torch.float32)
+        bias_dtype = bias.dtype
+        bias = bias.contiguous().to(side)
     y = torch.empty_like(x)
     if bias_grad_into is not None:
+        if bias_grad_into.dtype != side:
+            raise RuntimeError(f"fused_bias_act: bias_grad_into must be {side} for {x.dtype} tensors")
         bg, want_bias_grad = bias_grad_into, True
     else:
-        bg = torch.zeros(c, device=x.device, dtype=torch.float32) if want_bias_grad else None
+        bg = torch.zeros(c, device=x.device, dtype=side) if want_bias_grad else None
     if x.numel():
         rc = lib.ideas_fused_bias_act(_lib.ptr(y), _lib.ptr(x), _lib.ptr(bias), _lib.ptr(ref), _lib.ptr(bg),
                                       x.numel(), c, inner, layout, act, grad, float(alpha), float(scale), dt,
@@ -83,6 +90,8 @@ def bias_act_raw(x: torch.Tensor, bias: Optional[torch.Tensor], ref: Optional[to
         _lib.check(rc, "ideas_fused_bias_act")
     if bias_grad_into is not None:
         return y, None
+    if bg is not None and dt in (_lib.F16, _lib.F64):
+        bg = bg.to(bias_dtype or x.dtype)                 # autograd wants the gradient in the parameter's dtype
     return (y, bg) if want_bias_grad else y
 
 
@@ -112,7 +121,7 @@ def bias_sink(bias: Optional[torch.Tensor]):
         return None
     from .conv import _sink_target
     tgt = _sink_target(bias)
-    return tgt if (tgt is not None and tgt.dim() == 1 and tgt.is_contiguous()) else None
+    return tgt if (tgt is not None and tgt.dim() == 1 and tgt.is_contiguous() and tgt.dtype == torch.float32) else None
 
 
 class FusedLeakyReLUFunctionBackward(Function):

@@ -18,9 +18,10 @@ from .. import _lib
 
 def upfirdn2d_raw(x: torch.Tensor, fir: torch.Tensor, up: Tuple[int, int], down: Tuple[int, int],
                   pad: Tuple[int, int, int, int], out_hw: Tuple[int, int], flip: bool, gain: float = 1.0) -> torch.Tensor:
-    """One launch.  ``pad = (x0, x1, y0, y1)``; ``flip=True`` is the op's own (correlate-with-flipped-FIR) semantics."""
+    """One launch.  ``pad = (x0, x1, y0, y1)``; ``flip=True`` is the op's own (correlate-with-flipped-FIR) semantics.
+    Any FIR size; f32 / bf16 / f16 / f64 tensors (the FIR goes to f64 for f64 tensors, to f32 otherwise)."""
     _lib.require_cuda(x, fir)
-    dt = _lib.act_dtype(x)
+    dt = _lib.op_dtype(x)
     if x.dim() != 4:
         raise RuntimeError("upfirdn2d expects a 4-D [B, C, H, W] tensor")
     lib = _lib.load()
@@ -31,12 +32,12 @@ def upfirdn2d_raw(x: torch.Tensor, fir: torch.Tensor, up: Tuple[int, int], down:
         raise RuntimeError(f"upfirdn2d: empty output {oh}x{ow}")
     if x.is_contiguous(memory_format=torch.channels_last):
         layout, fmt = _lib.NHWC, torch.channels_last
-    elif x.is_contiguous() and dt == _lib.F32:
+    elif x.is_contiguous() and dt != _lib.BF16:          # (the bf16 kernels are NHWC-only)
         layout, fmt = _lib.NCHW, torch.contiguous_format
     else:
         x = x.contiguous(memory_format=torch.channels_last)
         layout, fmt = _lib.NHWC, torch.channels_last
-    fir = fir.contiguous().to(torch.float32)
+    fir = fir.contiguous().to(torch.float64 if dt == _lib.F64 else torch.float32)
     y = torch.empty((b, c, oh, ow), device=x.device, dtype=x.dtype, memory_format=fmt)
     rc = lib.ideas_upfirdn2d(_lib.ptr(y), _lib.ptr(x), _lib.ptr(fir), b, c, h, w, oh, ow, kh, kw, up[0], up[1],
                              down[0], down[1], pad[0], pad[2], float(gain), int(flip), layout, dt,
@@ -49,8 +50,8 @@ BLUR_ACT_BWD, BLUR_BIAS_ACT = 1, 2
 
 
 def blur_fused_ok(x: torch.Tensor, fir: torch.Tensor) -> bool:
-    """Geometry the fused blur kernels take: channels_last 4-D tensor, C % 4 == 0, 4x4 FIR."""
-    return (x.dim() == 4 and x.is_cuda and x.shape[1] % 4 == 0 and tuple(fir.shape) == (4, 4)
+    """Geometry the fused blur kernels take: f32 / bf16 channels_last 4-D tensor, C % 4 == 0, 4x4 FIR."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.shape[1] % 4 == 0 and tuple(fir.shape) == (4, 4)
             and x.is_contiguous(memory_format=torch.channels_last))
 
 

@@ -51,8 +51,14 @@ enum { IDEAS_NCHW = 0, IDEAS_NHWC = 1 };
  *   IDEAS_BF16    bf16 mixed precision (BASELINE.json configs[4]; the reference's ops dispatch half as well,
  *                 fused_bias_act_kernel.cu:78, upfirdn2d_kernel.cu:311): activations (x, y, gy, resid) are bf16 in HBM,
  *                 contraction on v_mfma_f32_32x32x16_bf16 with f32 accumulation and an f32 epilogue; weights stay f32 masters
- *                 (the MFMA kernels read a bf16 pack of them, ideas_bf16_pack_weights), scales / biases / weight gradients f32. */
-enum { IDEAS_F32 = 0, IDEAS_F32_B3 = 1, IDEAS_BF16 = 2 };
+ *                 (the MFMA kernels read a bf16 pack of them, ideas_bf16_pack_weights), scales / biases / weight gradients f32.
+ * Two more values are taken ONLY by ideas_fused_bias_act and ideas_upfirdn2d (the reference's ops dispatch float, double and half,
+ * fused_bias_act_kernel.cu:78, upfirdn2d_kernel.cu:311); every other entry point returns IDEAS_E_UNSUPPORTED for them:
+ *   IDEAS_F16     half activations (_Float16 in HBM), f32 arithmetic, one rounding to half at the store.
+ *   IDEAS_F64     double activations and double arithmetic; the f32 side arguments of those two calls (bias, bias_grad, fir) are
+ *                 then double as well -- the pointer is passed through as the element type the dtype names.
+ * (Additive within ABI 4: no signature changed; an older library answers IDEAS_E_UNSUPPORTED.) */
+enum { IDEAS_F32 = 0, IDEAS_F32_B3 = 1, IDEAS_BF16 = 2, IDEAS_F16 = 3, IDEAS_F64 = 4 };
 
 enum {
     IDEAS_OK = 0,
@@ -86,6 +92,10 @@ int ideas_stream_destroy(void* stream);
  * [B,C] matrix is inner = 1).  `ref` is required iff grad == 1.  `bias_grad` (optional, grad == 1 only):
  * if non-NULL it must be a ZEROED float[C]; the kernel adds sum over (n,h,w) of y into it, fusing the
  * reference's separate grad_input.sum(dim) pass (fused_act.py:33-38).
+ * dtypes: IDEAS_F32 and IDEAS_F16 (x, y, ref half; b, bias_grad f32; f32 arithmetic in act's operation order, rounded once at the
+ * store) in NCHW, NHWC and [B,C]; IDEAS_BF16 in NHWC and [B,C]; IDEAS_F64 in all three, with x, y, ref, b AND bias_grad double
+ * (`bias_grad` is then a double* passed as float*).  `alpha` / `scale` are float for every dtype (the reference's binding takes
+ * float alpha, scale, fused_bias_act.cpp:12, and widens them).
  * ---------------------------------------------------------------------------------------------- */
 int ideas_fused_bias_act(void* y, const void* x, const void* b, const void* ref, float* bias_grad,
                          int64_t n, int C, int64_t inner, int layout,
@@ -100,7 +110,9 @@ int ideas_channel_sum(float* out, const void* x, int64_t n, int C, int clear, in
  * upfirdn2d.  Replaces upfirdn2d_op (upfirdn2d_kernel.cu:209-368): zero-stuff by `up`, pad (negative pad
  * crops), correlate with the FLIPPED kh x kw FIR, decimate by `down`.  x is [B,C,in_h,in_w] (NCHW) or
  * [B,in_h,in_w,C] (NHWC); y has out = (in*up + pad0 + pad1 - k) / down + 1 per axis.  `fir` is a device
- * float[kh*kw], row-major, kh,kw <= 8.  `gain` multiplies the FIR (1.0f for the plain op).
+ * float[kh*kw], row-major, any kh, kw >= 1 (tables too large for LDS are read from global memory).  `gain` multiplies the FIR
+ * (1.0f for the plain op).  dtypes: IDEAS_F32 and IDEAS_F16 (f32 FIR, f32 accumulation) in both layouts, IDEAS_BF16 in NHWC,
+ * IDEAS_F64 in both layouts with `fir` a device double[kh*kw] (passed as float*) and double accumulation.
  * The gradient is the same call with up<->down swapped, the FIR flipped and
  * pads (k - p0 - 1, in*up - out*down + p0 - up + 1)  (upfirdn2d.py:111-114).
  * ---------------------------------------------------------------------------------------------- */

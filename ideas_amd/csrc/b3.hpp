@@ -13,29 +13,21 @@ constexpr int BK = 16;     // f32 K depth of one pipeline step = K of one bf16 M
 constexpr int ROWB = 32;   // bytes per LDS row (16 bf16)
 constexpr unsigned RSRC_FLAGS = 0x00020000u;   // raw buffer, 32-bit data format
 
-// two f32 -> one dword of two RNE bf16 (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f32(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float hi_f32(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
-
 // exact three-way split of four f32 into packed bf16 planes
 struct Split4 { uint2 p[3]; };
 __device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = pack_bf16(a, b);
-    const float ra = a - lo_f32(h), rb = b - hi_f32(h);
-    m = pack_bf16(ra, rb);
-    l = pack_bf16(ra - lo_f32(m), rb - hi_f32(m));   // exact: <= 8 significant bits are left
+    h = ideas_pk_bf16(a, b);
+    const float ra = a - ideas_bf_lo(h), rb = b - ideas_bf_hi(h);
+    m = ideas_pk_bf16(ra, rb);
+    l = ideas_pk_bf16(ra - ideas_bf_lo(m), rb - ideas_bf_hi(m));   // exact: <= 8 significant bits are left
 }
 // the same from doubles (operands that are sums of f32 values, e.g. Winograd-transformed weights): the residuals are carried in
 // double, so the three planes hold the leading ~26 bits of the EXACT value instead of those of its f32 rounding
 __device__ __forceinline__ void split2d(double a, double b, unsigned& h, unsigned& m, unsigned& l) {
-    h = pack_bf16((float)a, (float)b);
-    const double ra = a - (double)lo_f32(h), rb = b - (double)hi_f32(h);
-    m = pack_bf16((float)ra, (float)rb);
-    l = pack_bf16((float)(ra - (double)lo_f32(m)), (float)(rb - (double)hi_f32(m)));
+    h = ideas_pk_bf16((float)a, (float)b);
+    const double ra = a - (double)ideas_bf_lo(h), rb = b - (double)ideas_bf_hi(h);
+    m = ideas_pk_bf16((float)ra, (float)rb);
+    l = ideas_pk_bf16((float)(ra - (double)ideas_bf_lo(m)), (float)(rb - (double)ideas_bf_hi(m)));
 }
 __device__ __forceinline__ Split4 split4(float4 v) {
     Split4 s;
@@ -51,6 +43,12 @@ __device__ __forceinline__ float4 buffer_load4(__amdgpu_buffer_rsrc_t r, unsigne
     const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
     return make_float4(f.x, f.y, f.z, f.w);
 }
+
+// Byte offsets into the two swizzled LDS layouts of the b3 kernels.
+// pix_off: 32-byte rows (16 bf16 of one pixel / slot), the 16-byte half XOR-ed with bit 3 of the row.
+__device__ __forceinline__ int pix_off(int pix, int half) { return pix * ROWB + ((half ^ ((pix >> 3) & 1)) << 4); }
+// chunk_off: 128-byte rows of eight 16-byte chunks, the chunk XOR-swizzled (by 4) with bit 1 of the row.
+__device__ __forceinline__ int chunk_off(int r, int c) { return (r * 8 + (c ^ (((r >> 1) & 1) << 2))) * 16; }
 
 // plane pairs, smallest terms first
 constexpr int PA[6] = {2, 0, 1, 1, 0, 0};

@@ -56,6 +56,8 @@ __device__ __forceinline__ unsigned ideas_pk_bf16(float a, float b) {          /
     const f32x2_ t = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2_));
 }
+__device__ __forceinline__ float ideas_bf_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }            // its low element
+__device__ __forceinline__ float ideas_bf_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }    // its high element
 __device__ __forceinline__ float4 to_f4(float4 v) { return v; }
 __device__ __forceinline__ float4 to_f4(ideas_bf16x4 p) {
     return make_float4(__builtin_bit_cast(float, p.v.x << 16), __builtin_bit_cast(float, p.v.x & 0xffff0000u),
@@ -138,6 +140,9 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;
 }
+
+// argument check shared by the convolution entry points (conv_direct.hip)
+int check_conv(const ideas_conv_params* p);
 
 // ---- batched weight preparation (ideas_weight_prep_batched): one launch per derived form over a table of parameters -----------
 // The derived weights (split-bf16 planes, Winograd planes, bf16 packs) are remade after every optimiser step, one small launch

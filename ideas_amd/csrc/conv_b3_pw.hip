@@ -388,7 +388,6 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pwk_kernel(float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ int pw_chunk_off(int r, int c) { return (r * 8 + (c ^ (((r >> 1) & 1) << 2))) * 16; }
 
 __global__ __launch_bounds__(256, 2) void conv_b3_pw_wgrad_kernel(float* __restrict__ gw, const float* __restrict__ gy,
                                                                   const float* __restrict__ x, ideas_conv_params p, unsigned M,
@@ -426,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pw_wgrad_kernel(float* __restr
     };
     int lds_row[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) lds_row[k] = pw_chunk_off(px + 16 * k, quad >> 1) + (quad & 1) * 8;
+    for (int k = 0; k < 2; ++k) lds_row[k] = chunk_off(px + 16 * k, quad >> 1) + (quad & 1) * 8;
     auto lstore = [&](const Stage& st, int buf) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {

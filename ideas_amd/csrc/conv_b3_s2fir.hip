@@ -57,7 +57,6 @@ struct S2Fir {
     int XH, XW, pad0;          // raw input [B, XH, XW, Cin]; p.IH x p.IW is the blurred size
 };
 
-__device__ __forceinline__ int slot_byte(int slot, int half) { return slot * ROWB + ((half ^ ((slot >> 3) & 1)) << 4); }
 
 constexpr int NPW = 4;                         // producer (FIR) waves: one per SIMD
 #ifndef S2FIR_ABL
@@ -261,7 +260,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
     // immediates: + PITCH * ROWB per ty (halves swapped back for ty = 1), + ODD0 * ROWB for tx = 1, + 4 * PITCH * ROWB per row block
     // (bit 3 unchanged).
     const int a_row0 = (4 * wm * RB + 2 * (li >> 4)) * PITCH + (li & 15);
-    int a_c0 = slot_byte(a_row0, lh), a_c2 = slot_byte(a_row0 + 1, lh);
+    int a_c0 = pix_off(a_row0, lh), a_c2 = pix_off(a_row0 + 1, lh);
     auto a_off = [&](int tap, int rb) {
         const int ty = tap / 3, tx = tap - 3 * ty;
         static_assert(ODD0 % 8 == 0 && (ODD0 / 8) % 2 == 1, "tap column 1 = tap column 0's address with the halves swapped");

@@ -41,7 +41,6 @@ struct TPhase {
     int oh[4], ow[4], ooy[4], oox[4];
 };
 
-__device__ __forceinline__ int pix_off(int pix, int chunk16) { return pix * ROWB + ((chunk16 ^ ((pix >> 3) & 1)) << 4); }
 
 template <bool SCALE>
 __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restrict__ y, const float* __restrict__ x,

@@ -49,7 +49,6 @@ template <int S> struct W3 {
     static constexpr int XLOADS = (XW * 16 + 255) / 256;   // float4 loads per thread and window row: 2 / 3
 };
 
-__device__ __forceinline__ int chunk_off(int r, int c) { return (r * 8 + (c ^ (((r >> 1) & 1) << 2))) * 16; }
 
 template <int S, bool SCALE, bool REFLECT>
 __global__ __launch_bounds__(256, 2) void conv_b3_wgrad3_kernel(float* __restrict__ gw, const float* __restrict__ gy,

@@ -47,12 +47,6 @@ constexpr int ROW = 64;         // bytes per LDS row of the forward kernel
 constexpr unsigned RSRC = 0x00020000u;
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    const f32x2v v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-__device__ __forceinline__ float bf_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
 __device__ __forceinline__ uint4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(uint4* __restrict__ d
             v = make_float4(v.x * s1.x, v.y * s1.y, v.z * s1.z, v.w * s1.w);
         }
         out[((int64_t)step * Cout + n) * 4 + (c ^ ((n >> 2) & 3))] =
-            make_uint4(pk_bf16(u.x, u.y), pk_bf16(u.z, u.w), pk_bf16(v.x, v.y), pk_bf16(v.z, v.w));
+            make_uint4(ideas_pk_bf16(u.x, u.y), ideas_pk_bf16(u.z, u.w), ideas_pk_bf16(v.x, v.y), ideas_pk_bf16(v.z, v.w));
     }
 }
 
@@ -128,7 +122,7 @@ __device__ __forceinline__ void pack_weights_strided_body(uint4* __restrict__ ds
         const int step = (ci >> 5) * ntaps + tap;
         const int c = (ci & 31) >> 3;
         out[((int64_t)step * Cout + n) * 4 + (c ^ ((n >> 2) & 3))] =
-            make_uint4(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7]));
+            make_uint4(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]), ideas_pk_bf16(v[4], v[5]), ideas_pk_bf16(v[6], v[7]));
     }
 }
 
@@ -372,10 +366,10 @@ __device__ __forceinline__ void conv_bf16_body(bf16_t* __restrict__ y, const bf1
                 const float bvv[4] = {bv.x, bv.y, bv.z, bv.w}, osv[4] = {os.x, os.y, os.z, os.w};
                 uint2 rr = make_uint2(0u, 0u);
                 if (resid) rr = *reinterpret_cast<const uint2*>(resid + off + n);
-                const float rv[4] = {bf_lo(rr.x), bf_hi(rr.x), bf_lo(rr.y), bf_hi(rr.y)};
+                const float rv[4] = {ideas_bf_lo(rr.x), ideas_bf_hi(rr.x), ideas_bf_lo(rr.y), ideas_bf_hi(rr.y)};
                 uint2 prev = make_uint2(0u, 0u);
                 if (p.accumulate) prev = *reinterpret_cast<const uint2*>(y + off + n);
-                const float pv[4] = {bf_lo(prev.x), bf_hi(prev.x), bf_lo(prev.y), bf_hi(prev.y)};
+                const float pv[4] = {ideas_bf_lo(prev.x), ideas_bf_hi(prev.x), ideas_bf_lo(prev.y), ideas_bf_hi(prev.y)};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float u = acc[a][b][4 * g + j] * p.gain * osv[j] + bvv[j];
@@ -384,7 +378,7 @@ __device__ __forceinline__ void conv_bf16_body(bf16_t* __restrict__ y, const bf1
                     if (p.accumulate) u += pv[j];
                     v[j] = u;
                 }
-                q[g] = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
+                q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
                 if (!wide) *reinterpret_cast<uint2*>(y + off + n) = q[g];
             }
             if (wide) {                                      // (block-uniform; every lane takes part in the exchange)
@@ -658,10 +652,10 @@ __global__ __launch_bounds__(512, 4) void conv_bf16_img_kernel(bf16_t* __restric
                 const float bvv[4] = {bv.x, bv.y, bv.z, bv.w}, osv[4] = {os.x, os.y, os.z, os.w};
                 uint2 rr = make_uint2(0u, 0u);
                 if (resid) rr = *reinterpret_cast<const uint2*>(resid + off + n);
-                const float rv[4] = {bf_lo(rr.x), bf_hi(rr.x), bf_lo(rr.y), bf_hi(rr.y)};
+                const float rv[4] = {ideas_bf_lo(rr.x), ideas_bf_hi(rr.x), ideas_bf_lo(rr.y), ideas_bf_hi(rr.y)};
                 uint2 prev = make_uint2(0u, 0u);
                 if (p.accumulate) prev = *reinterpret_cast<const uint2*>(y + off + n);
-                const float pv[4] = {bf_lo(prev.x), bf_hi(prev.x), bf_lo(prev.y), bf_hi(prev.y)};
+                const float pv[4] = {ideas_bf_lo(prev.x), ideas_bf_hi(prev.x), ideas_bf_lo(prev.y), ideas_bf_hi(prev.y)};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float u = acc[a][b][4 * g + j] * p.gain * osv[j] + bvv[j];
@@ -670,7 +664,7 @@ __global__ __launch_bounds__(512, 4) void conv_bf16_img_kernel(bf16_t* __restric
                     if (p.accumulate) u += pv[j];
                     v[j] = u;
                 }
-                q[g] = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
+                q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
                 if (!wide) *reinterpret_cast<uint2*>(y + off + n) = q[g];
             }
             if (wide) {                                      // (block-uniform; every lane takes part in the exchange)

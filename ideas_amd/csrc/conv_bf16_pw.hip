@@ -30,12 +30,6 @@ namespace {
 constexpr unsigned RSRC = 0x00020000u;
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    const f32x2v v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-__device__ __forceinline__ float bf_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
 template <int N> __device__ __forceinline__ void wait_step() {       // (conv_bf16.hip: the LDS reads must have returned as well)
     static_assert(N >= 0 && N <= 63, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_pw_kernel(bf16_t* __restrict
                         }
                         uint2 rq = make_uint2(0u, 0u);
                         if (resid) rq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rr, (int)(ok ? yrow + (unsigned)n * 2u : 0xffffffffu), 0, 0));
-                        const float rv[4] = {bf_lo(rq.x), bf_hi(rq.x), bf_lo(rq.y), bf_hi(rq.y)};
+                        const float rv[4] = {ideas_bf_lo(rq.x), ideas_bf_hi(rq.x), ideas_bf_lo(rq.y), ideas_bf_hi(rq.y)};
                         float v[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -182,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_pw_kernel(bf16_t* __restrict
                             if (resid) u = (u + rv[j]) * p.resid_gain;
                             v[j] = u;
                         }
-                        q[g] = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
+                        q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
                     }
                     uint4 ch[2];
                     quad_exchange(q, ch);

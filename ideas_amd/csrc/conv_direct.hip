@@ -382,15 +382,6 @@ bool is_pointwise(const ideas_conv_params* p) {
            p->osx == 1 && p->ooy == 0 && p->oox == 0 && p->IH == p->OH && p->IW == p->OW && p->YH == p->OH && p->YW == p->OW;
 }
 
-int check_conv(const ideas_conv_params* p) {
-    if (!p) return IDEAS_E_NULL;
-    if (p->B <= 0 || p->IH <= 0 || p->IW <= 0 || p->Cin <= 0 || p->YH <= 0 || p->YW <= 0 || p->Cout <= 0) return IDEAS_E_SHAPE;
-    if (p->OH <= 0 || p->OW <= 0 || p->TY <= 0 || p->TX <= 0 || p->osy <= 0 || p->osx <= 0) return IDEAS_E_SHAPE;
-    if ((p->OH - 1) * p->osy + p->ooy >= p->YH || (p->OW - 1) * p->osx + p->oox >= p->YW || p->ooy < 0 || p->oox < 0)
-        return IDEAS_E_SHAPE;
-    return IDEAS_OK;
-}
-
 template <typename T>
 int conv_direct_impl(void* y, const void* x, const void* wmat, const float* in_scale, const float* out_scale, const float* bias,
                      const void* resid, const ideas_conv_params* p, void* stream) {
@@ -491,6 +482,15 @@ int wgrad_direct_impl(float* gw, const void* gy, const void* x, const float* in_
 }
 
 }  // namespace
+
+int check_conv(const ideas_conv_params* p) {
+    if (!p) return IDEAS_E_NULL;
+    if (p->B <= 0 || p->IH <= 0 || p->IW <= 0 || p->Cin <= 0 || p->YH <= 0 || p->YW <= 0 || p->Cout <= 0) return IDEAS_E_SHAPE;
+    if (p->OH <= 0 || p->OW <= 0 || p->TY <= 0 || p->TX <= 0 || p->osy <= 0 || p->osx <= 0) return IDEAS_E_SHAPE;
+    if ((p->OH - 1) * p->osy + p->ooy >= p->YH || (p->OW - 1) * p->osx + p->oox >= p->YW || p->ooy < 0 || p->oox < 0)
+        return IDEAS_E_SHAPE;
+    return IDEAS_OK;
+}
 
 extern "C" int ideas_conv_check_params(const ideas_conv_params* p) { return check_conv(p); }
 

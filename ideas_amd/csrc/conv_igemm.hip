@@ -471,15 +471,6 @@ __global__ __launch_bounds__(256, SCALE ? 3 : 4) void conv_wgrad_kernel(float* _
     }
 }
 
-int check_conv(const ideas_conv_params* p) {
-    if (!p) return IDEAS_E_NULL;
-    if (p->B <= 0 || p->IH <= 0 || p->IW <= 0 || p->Cin <= 0 || p->YH <= 0 || p->YW <= 0 || p->Cout <= 0) return IDEAS_E_SHAPE;
-    if (p->OH <= 0 || p->OW <= 0 || p->TY <= 0 || p->TX <= 0 || p->osy <= 0 || p->osx <= 0) return IDEAS_E_SHAPE;
-    if ((p->OH - 1) * p->osy + p->ooy >= p->YH || (p->OW - 1) * p->osx + p->oox >= p->YW || p->ooy < 0 || p->oox < 0)
-        return IDEAS_E_SHAPE;
-    return IDEAS_OK;
-}
-
 template <int WM, int WN, int MT, int NT>
 int launch_fwd_cfg(void* y, const void* x, const void* wmat, const float* in_scale, const float* out_scale,
                    const float* bias, const void* resid, const ideas_conv_params* p, hipStream_t stream) {

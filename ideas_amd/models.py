@@ -29,6 +29,7 @@ from .precision import to_act, to_f32
 _INV_SQRT2 = 1.0 / math.sqrt(2)
 FUSE_RESIDUAL_ADDS = True     # big residual blocks: block input forked by one autograd node (gradient sum / merge add ride in kernels)
 FUSE_BLUR_CONV = os.environ.get("IDEAS_BLUR_CONV", "1") != "0"   # downsampling ResBlock body with conv2's Blur inside its conv kernel
+DCO_MERGE = os.environ.get("IDEAS_DCO_MERGE", "2")               # CooccurDiscriminator.forward_pair: encoder passes merged (A/B)
 FUSE_BLUR_BACKWARD = True     # ResBlock: conv1 + conv2's Blur as one Function whose backward is one kernel (A/B switch for tools / tests)
 
 
@@ -433,7 +434,7 @@ class CooccurenceDiscriminator(nn.Module):
         Same box, two interleaved runs (profiles/r06_dco_merge_ab.txt, r06_dco_merge3_ab.txt): three passes 400.1 ms, fake + real
         merged 397.8 / 395.8, all three merged 394.5; bf16 150.5 / 148.7 / 147.0.  (Round 3 measured the full merge 0.8 % SLOWER in
         f32 -- on that round's kernels; IDEAS_DCO_MERGE=0 / 1 restore three passes / the fake + real merge for A/B runs.)"""
-        mode = os.environ.get("IDEAS_DCO_MERGE", "2")
+        mode = DCO_MERGE
         plain = not fake.requires_grad and not real.requires_grad and not reference.requires_grad and fake.shape[1:] == real.shape[1:] == reference.shape[1:]
         nf, nr = fake.shape[0], real.shape[0]
         if plain and mode == "2":

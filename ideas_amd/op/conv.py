@@ -12,25 +12,45 @@ All activations are NHWC in memory (``torch.channels_last`` on a logical [B,C,H,
 from __future__ import annotations
 
 import ctypes as C
+import os as _os
 from typing import List, Optional, Tuple
 
 import torch
 from torch.autograd import Function
 
 from .. import _lib
-from ..precision import to_act
+from ..precision import activation_dtype, to_act
 from . import conv_plan
 from .conv_plan import ConvGeom, Launch, convT_out_size, plan_dgrad, plan_fwd, plan_wgrad
+from .fused_act import FusedLeakyReLUFunctionBackward, bias_act_raw, bias_sink, channel_sum
+from .grad_sink import _SINK, _sink_target, grad_sink, weight_grad      # noqa: F401  (re-exported: the sink's old home)
+from .upfirdn2d import BLUR_ACT_BWD, UpFirDn2dBackward, blur_fused_ok, blur_fused_raw, blur_geometry, upfirdn2d_raw
 
 CL = torch.channels_last
+BF = torch.bfloat16
 
+# ---- switches, each read once at import; the functions below read them from the module's globals at call time ----
 # 1-D Winograd F(2,3) for the 3x3 / stride-1 / pad-1 layers (csrc/conv_wino.hip): 1.5x fewer MFMAs.
 # IDEAS_WINOGRAD=0 falls back to the direct implicit GEMM (A/B measurements, debugging).
-import os as _os
 WINOGRAD = _os.environ.get("IDEAS_WINOGRAD", "1") != "0"
 # Contraction arithmetic of the MFMA convolutions (include/ideas_hip.h): "f32" = f32 matrix instruction, "b3" = exact
 # 3-way bf16 split + six bf16 MFMA products (f32-class error, 2.67x the matrix rate).
 MATH = {"f32": _lib.F32, "b3": _lib.F32_B3}[_os.environ.get("IDEAS_MATH", "b3")]
+# Winograd F(2,3) variant of the split-bf16 kernel for the 3x3/s1/p1 layers (csrc/conv_b3_wino.hip); IDEAS_B3_WINO=0 keeps them
+# on the direct split kernel.
+B3_WINO = _os.environ.get("IDEAS_B3_WINO", "1") != "0"
+# (diagnostics) the Winograd kernel for the forward convs only / the input gradients only
+B3_WINO_FWD = _os.environ.get("IDEAS_B3_WINO_FWD", "1") != "0"
+B3_WINO_DGRAD = _os.environ.get("IDEAS_B3_WINO_DGRAD", "1") != "0"
+B3_MULTI = _os.environ.get("IDEAS_B3_MULTI", "1") != "0"
+PRESCALE_MOD_PIX = int(_os.environ.get("IDEAS_PRESCALE_MOD_PIX", "256"))
+_BIAS_SUM_HIP = _os.environ.get("IDEAS_BIAS_SUM_HIP", "1") != "0"      # 0: autograd's composite sum (A/B only)
+# Blur -> 3x3 / stride-2 conv (+ bias + leaky-ReLU) of a downsampling ConvLayer in ONE kernel (csrc/conv_b3_s2fir.hip): the
+# blurred tensor is built in LDS under each output patch and never makes the round trip through HBM.  IDEAS_BLUR_CONV=0 keeps the
+# blur a separate pass (A/B measurements).
+BLUR_CONV = _os.environ.get("IDEAS_BLUR_CONV", "1") != "0"
+BLUR_CONV_MIN_OW = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_OW", "16"))      # below: the 8 x 16 output patch of the kernel would idle
+BLUR_CONV_MIN_BLOCKS = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_BLOCKS", "512"))   # down_pair_ok: below, the two-kernel chain wins
 
 
 def wino_weights(w_ohwi: torch.Tensor) -> torch.Tensor:
@@ -49,38 +69,40 @@ def _wino_ok(g: "ConvGeom", cin: int, width: int, fwd: bool = True) -> bool:
     return WINOGRAD and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and width % 2 == 0 and cin % 8 == 0
 
 
-# Winograd F(2,3) variant of the split-bf16 kernel for the 3x3/s1/p1 layers (csrc/conv_b3_wino.hip); IDEAS_B3_WINO=0 keeps them
-# on the direct split kernel.
-B3_WINO = _os.environ.get("IDEAS_B3_WINO", "1") != "0"
-# (diagnostics) the Winograd kernel for the forward convs only / the input gradients only
-B3_WINO_FWD = _os.environ.get("IDEAS_B3_WINO_FWD", "1") != "0"
-B3_WINO_DGRAD = _os.environ.get("IDEAS_B3_WINO_DGRAD", "1") != "0"
-
-
 def _b3_wino_ok(g: "ConvGeom", cin: int, cout: int, width: int) -> bool:
     return (MATH == _lib.F32_B3 and B3_WINO and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and width % 2 == 0
             and cin % 16 == 0 and cout % 4 == 0)
 
 
+def _prep(op: int, planes: int, taps: int, dims, strides, src: int, vec: int, aligned: bool = True):
+    """The ``prep`` tuple of ``conv_plan.cached`` for a derived-weight form of ``planes`` bf16 planes over ``taps`` x prod(``dims``)
+    elements, read ``vec`` channels (the last of ``dims``) at a time through ``strides`` from address ``src``: the same call as one
+    entry of the batched refill.  None where the batched kernels' channel granularity (4 * vec) does not divide the channels.
+    ``aligned``: the form has a 16-byte fast path, taken for unit channel stride and 16-byte aligned rows."""
+    if dims[-1] % (4 * vec):
+        return None
+    n = taps
+    for d in dims:
+        n *= d
+    unit = aligned and strides[3] == 1 and src % 16 == 0 and strides[0] % 4 == 0 and strides[1] % 4 == 0 and strides[2] % 4 == 0
+    return (op, planes * n, tuple(dims), tuple(strides), unit, src, n // vec)
+
+
 def b3_wino_planes(w: torch.Tensor, transposed: bool) -> torch.Tensor:
     """Winograd-transformed, split weights of a [O,I,3,3] parameter for ideas_conv3x3_wino(IDEAS_F32_B3): the forward matrix,
     or (transposed) the flipped one of the input gradient, read straight from the OHWI memory of the parameter."""
-    def make():
-        o, i = w.shape[0], w.shape[1]
-        wm = w.permute(0, 2, 3, 1)
-        wm = wm if wm.is_contiguous() else wm.contiguous()
-        n, c, sn, sky, skx, sc, base = (i, o, 1, -3 * i, -i, 9 * i, 8 * i) if transposed else (o, i, 9 * i, 3 * i, i, 1, 0)
-        pl = torch.empty(12 * n * 3 * c, device=w.device, dtype=torch.bfloat16)
-        _lib.check(_lib.load().ideas_b3_wino_split_weights(_lib.ptr(pl), _lib.ptr(wm), n, c, sn, sky, skx, sc, base,
-                                                            _lib.stream_ptr()), "ideas_b3_wino_split_weights")
-        return pl
-    prep = None
+    o, i = w.shape[0], w.shape[1]
+    n, c, *st = (i, o, 1, -3 * i, -i, 9 * i, 8 * i) if transposed else (o, i, 9 * i, 3 * i, i, 1, 0)
     wm0 = w.permute(0, 2, 3, 1)
-    if wm0.is_contiguous() and w.shape[1] % 16 == 0:        # read in place: the same call as an entry of the batched refill
-        o, i = w.shape[0], w.shape[1]
-        n, c, sn, sky, skx, sc, base = (i, o, 1, -3 * i, -i, 9 * i, 8 * i) if transposed else (o, i, 9 * i, 3 * i, i, 1, 0)
-        if c % 16 == 0:
-            prep = (_lib.PREP_B3_WINO, 12 * n * 3 * c, (n, c), (sn, sky, skx, sc, base), 0, wm0.data_ptr(), n * 3 * (c // 4))
+
+    def make():
+        wm = wm0 if wm0.is_contiguous() else wm0.contiguous()
+        pl = torch.empty(12 * n * 3 * c, device=w.device, dtype=BF)
+        _lib.check(_lib.load().ideas_b3_wino_split_weights(_lib.ptr(pl), _lib.ptr(wm), n, c, *st, _lib.stream_ptr()),
+                   "ideas_b3_wino_split_weights")
+        return pl
+    # read in place: the same call as an entry of the batched refill
+    prep = _prep(_lib.PREP_B3_WINO, 12, 3, (n, c), st, wm0.data_ptr(), 4, aligned=False) if wm0.is_contiguous() and i % 16 == 0 else None
     return conv_plan.cached(w, ("b3wino", transposed), make, prep)
 
 
@@ -97,9 +119,6 @@ def _nhwc(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32 and t.dtype != torch.bfloat16:
         raise RuntimeError(f"ideas_amd conv: only float32 and bfloat16 activations are implemented, got {t.dtype}")
     return t if t.is_contiguous(memory_format=CL) else t.contiguous(memory_format=CL)
-
-
-BF = torch.bfloat16
 
 
 def _f32(t):
@@ -126,10 +145,7 @@ def bf16_pack(L: Launch, in_scale=None) -> torch.Tensor:
         return make()
     if in_scale is not None:           # per-sample packs: the same (weights, styles) pair comes back within an iteration (conv_plan.cached_on)
         return conv_plan.cached_on(L.wsrc, ("bf16s",) + L.wkey, in_scale, make, budget=True)
-    sn, sty, stx, sc = v.stride()
-    unit = sc == 1 and v.data_ptr() % 16 == 0 and sn % 4 == 0 and sty % 4 == 0 and stx % 4 == 0
-    prep = (_lib.PREP_BF16_PACK, L.Cout * L.TY * L.TX * L.Cin, (L.Cout, L.TY, L.TX, L.Cin), (sn, sty, stx, sc), unit, v.data_ptr(),
-            L.Cout * L.TY * L.TX * (L.Cin // 8)) if L.Cin % 32 == 0 else None
+    prep = _prep(_lib.PREP_BF16_PACK, 1, 1, (L.Cout, L.TY, L.TX, L.Cin), v.stride(), v.data_ptr(), 8)
     return conv_plan.cached(L.wsrc, ("bf16",) + L.wkey, make, prep)
 
 
@@ -145,10 +161,7 @@ def b3_planes(L: Launch) -> torch.Tensor:
         return pl
     if L.wsrc is None:
         return split()
-    sn, sty, stx, sc = v.stride()
-    unit = sc == 1 and v.data_ptr() % 16 == 0 and sn % 4 == 0 and sty % 4 == 0 and stx % 4 == 0
-    prep = (_lib.PREP_B3_SPLIT, 3 * L.Cout * L.TY * L.TX * L.Cin, (L.Cout, L.TY, L.TX, L.Cin), (sn, sty, stx, sc), unit, v.data_ptr(),
-            L.Cout * L.TY * L.TX * (L.Cin // 4)) if L.Cin % 16 == 0 else None
+    prep = _prep(_lib.PREP_B3_SPLIT, 3, 1, (L.Cout, L.TY, L.TX, L.Cin), v.stride(), v.data_ptr(), 4)
     return conv_plan.cached(L.wsrc, ("b3",) + L.wkey, split, prep)
 
 
@@ -191,9 +204,6 @@ def launch_fwd(y: torch.Tensor, x: torch.Tensor, L: Launch, gain: float, in_scal
     rc = fn(_lib.ptr(y), _lib.ptr(x), _lib.ptr(L.wmat), _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(bias),
             _lib.ptr(resid), C.byref(p), _lib.F32, _lib.stream_ptr())
     _lib.check(rc, "ideas_conv_igemm" if L.Cin % 4 == 0 else "ideas_conv_direct")
-
-
-B3_MULTI = _os.environ.get("IDEAS_B3_MULTI", "1") != "0"
 
 
 def launch_multi(y: torch.Tensor, x: torch.Tensor, launches, gain: float, in_scale=None, out_scale=None) -> bool:
@@ -256,24 +266,35 @@ def launch_wgrad(gw: torch.Tensor, gy: torch.Tensor, x: torch.Tensor, L: Launch,
 # lout = per-(b, output-channel) scale of the launch.
 # ----------------------------------------------------------------------------------------------------
 
+def _wino_conv(x, w, g: ConvGeom, gain: float, transposed: bool, lin=None, lout=None, bias=None, resid=None, act=False,
+               alpha=0.2, act_gain=1.0, resid_gain=1.0):
+    """A 3x3 / stride-1 / pad-1 conv of ``x`` with the [O,I,3,3] parameter ``w`` on a Winograd kernel (split-bf16, else f32), or
+    ``transposed`` its input gradient: the same conv with the taps flipped and the channel roles swapped.  None when neither
+    kernel applies."""
+    if x.dtype != torch.float32:
+        return None
+    b, cin, h, wd = x.shape
+    cout = w.shape[1 if transposed else 0]
+    if (B3_WINO_DGRAD if transposed else B3_WINO_FWD) and _b3_wino_ok(g, cin, cout, wd):
+        u, dtype = b3_wino_planes(w, transposed), _lib.F32_B3
+    elif _wino_ok(g, cin, wd):
+        u = wino_weights(w.flip(2, 3).permute(1, 2, 3, 0) if transposed else w.permute(0, 2, 3, 1))     # [n, ky, kx, c]
+        dtype = _lib.F32
+    else:
+        return None
+    y = torch.empty((b, cout, h, wd), device=x.device, dtype=x.dtype, memory_format=CL)
+    launch_wino(y, x, u, b, cin, h, wd, cout, gain, g.reflect, lin, lout, bias, resid, act=act, alpha=alpha, act_gain=act_gain,
+                resid_gain=resid_gain, dtype=dtype)
+    return y
+
+
 def conv_fwd_raw(x, w, g: ConvGeom, gain: float, lin=None, lout=None, bias=None, act=False, act_gain=1.0,
                  resid=None, resid_gain=1.0, alpha=0.2):
     x = _nhwc(x)
     if resid is not None:
         resid = _nhwc(resid)
-    if x.dtype == torch.float32 and B3_WINO_FWD and _b3_wino_ok(g, x.shape[1], w.shape[0], x.shape[3]):
-        b, ci, h, wd = x.shape
-        co = w.shape[0]
-        y = torch.empty((b, co, h, wd), device=x.device, dtype=x.dtype, memory_format=CL)
-        launch_wino(y, x, b3_wino_planes(w, False), b, ci, h, wd, co, gain, g.reflect, lin, lout, bias, resid, act=act,
-                    alpha=alpha, act_gain=act_gain, resid_gain=resid_gain, dtype=_lib.F32_B3)
-        return y
-    if x.dtype == torch.float32 and _wino_ok(g, x.shape[1], x.shape[3]):
-        b, ci, h, wd = x.shape
-        co = w.shape[0]
-        y = torch.empty((b, co, h, wd), device=x.device, dtype=x.dtype, memory_format=CL)
-        launch_wino(y, x, wino_weights(w.permute(0, 2, 3, 1)), b, ci, h, wd, co, gain, g.reflect, lin, lout, bias, resid,
-                    act=act, alpha=alpha, act_gain=act_gain, resid_gain=resid_gain)
+    y = _wino_conv(x, w, g, gain, False, lin, lout, bias, resid, act, alpha, act_gain, resid_gain)
+    if y is not None:
         return y
     L = plan_fwd(x.shape, w, g)
     y = torch.empty((L.B, L.Cout, L.YH, L.YW), device=x.device, dtype=x.dtype, memory_format=CL)
@@ -301,27 +322,15 @@ def conv_dgrad_raw(gy, w, g: ConvGeom, in_hw: Tuple[int, int], gain: float, lin=
         ph, pw = in_hw[0] + 2 * g.pad, in_hw[1] + 2 * g.pad
         gxp = conv_dgrad_raw(gy, w, gp, (ph, pw), gain, lin, lout)
         b, c = gxp.shape[0], gxp.shape[1]
-        gx = torch.empty((b, c, in_hw[0], in_hw[1]), device=gxp.device, dtype=gxp.dtype, memory_format=CL)
         if gxp.dtype == BF and c % 4:
             return conv_dgrad_fold32(gxp, in_hw, g.pad)
+        gx = torch.empty((b, c, in_hw[0], in_hw[1]), device=gxp.device, dtype=gxp.dtype, memory_format=CL)
         rc = _lib.load().ideas_reflect_fold(_lib.ptr(gx), _lib.ptr(gxp), b, in_hw[0], in_hw[1], c, g.pad, _lib.act_dtype(gxp),
                                             _lib.stream_ptr())
         _lib.check(rc, "ideas_reflect_fold")
         return gx
-    f32 = gy.dtype == torch.float32
-    if f32 and B3_WINO_DGRAD and in_hw == (gy.shape[2], gy.shape[3]) and _b3_wino_ok(g, gy.shape[1], w.shape[1], gy.shape[3]):
-        b, co, h, wd = gy.shape
-        ci = w.shape[1]
-        gx = torch.empty((b, ci, h, wd), device=gy.device, dtype=gy.dtype, memory_format=CL)
-        launch_wino(gx, gy, b3_wino_planes(w, True), b, co, h, wd, ci, gain, False, lin, lout, dtype=_lib.F32_B3)
-        return gx
-    if f32 and in_hw == (gy.shape[2], gy.shape[3]) and _wino_ok(g, gy.shape[1], gy.shape[3]):
-        # dgrad of a 3x3/s1/p1 conv = the same conv with the taps flipped and the channel roles swapped
-        b, co, h, wd = gy.shape
-        ci = w.shape[1]
-        gx = torch.empty((b, ci, h, wd), device=gy.device, dtype=gy.dtype, memory_format=CL)
-        u = wino_weights(w.flip(2, 3).permute(1, 2, 3, 0))       # [I, ky', kx', O]
-        launch_wino(gx, gy, u, b, co, h, wd, ci, gain, False, lin, lout)
+    gx = _wino_conv(gy, w, g, gain, True, lin, lout) if in_hw == (gy.shape[2], gy.shape[3]) else None
+    if gx is not None:
         return gx
     launches, need_zero = plan_dgrad(gy.shape, w, g, in_hw)
     b, ci = gy.shape[0], w.shape[1]
@@ -347,13 +356,14 @@ def conv_dgrad_fold32(gxp: torch.Tensor, in_hw, pad: int) -> torch.Tensor:
 _GU = {}
 
 
-def _wino_gu_scratch(n: int, device) -> torch.Tensor:
-    """ZEROED f32 scratch for a Winograd-domain gradient dU, one per (stream, size) (a fold with ``clear`` re-zeroes it behind its read)."""
+def _wino_gu_scratch(n: int, device):
+    """ZEROED f32 scratch for a Winograd-domain gradient dU, one per (stream, size) (a fold with ``clear`` re-zeroes it behind its
+    read), and its key in ``_GU``: whoever fails between filling it and the fold drops the entry, since nothing re-zeroes it then."""
     key = (_lib.stream_ptr(), n, str(device))
     buf = _GU.get(key)
     if buf is None:
         buf = _GU[key] = torch.zeros(n, device=device, dtype=torch.float32)
-    return buf
+    return buf, key
 
 
 def _wino_fold(gu, out, co: int, ci: int, w_shape, device, clear: bool = True):
@@ -363,9 +373,6 @@ def _wino_fold(gu, out, co: int, ci: int, w_shape, device, clear: bool = True):
     rc = _lib.load().ideas_wino_wgrad_fold(_lib.ptr(tgt), _lib.ptr(gu), co, ci, so, sky, skx, si, int(clear), _lib.stream_ptr())
     _lib.check(rc, "ideas_wino_wgrad_fold")
     return tgt
-
-
-PRESCALE_MOD_PIX = int(_os.environ.get("IDEAS_PRESCALE_MOD_PIX", "256"))
 
 
 def conv_wgrad_raw(gy, x, g: ConvGeom, w_shape, gain: float, lin=None, lout=None, out=None):
@@ -392,18 +399,17 @@ def conv_wgrad_raw(gy, x, g: ConvGeom, w_shape, gain: float, lin=None, lout=None
     if not b3 and _wino_ok(g, x.shape[1], x.shape[3], fwd=False) and gy.shape[1] % 4 == 0 and tuple(w_shape[2:]) == (3, 3):
         b, ci, h, wd = x.shape
         co = gy.shape[1]
-        gu = _wino_gu_scratch(4 * co * 3 * ci, x.device)          # zeroed once; the fold re-zeroes it behind its read
+        gu, key = _wino_gu_scratch(4 * co * 3 * ci, x.device)     # zeroed once; the fold re-zeroes it behind its read
         p = _lib.ConvParams(b, h, wd, ci, h, wd, co, h, wd, 3, 3, 1, 1, 1, 1, -1, -1, 1, 1, 0, 0, int(g.reflect), 0, 0.2,
                             1.0, 1.0, 0, gain)
-        rc = _lib.load().ideas_conv3x3_wino_wgrad(_lib.ptr(gu), _lib.ptr(gy), _lib.ptr(x), _lib.ptr(lin), _lib.ptr(lout),
-                                                  C.byref(p), _lib.F32, _lib.stream_ptr())
-        _lib.check(rc, "ideas_conv3x3_wino_wgrad")
-        return _wino_fold(gu, out, co, ci, w_shape, x.device, clear=True)
-    if (lin is None) != (lout is None):   # the MFMA wgrad kernel takes both per-sample scales or neither
-        if lin is None:
-            lin = torch.ones((x.shape[0], x.shape[1]), device=x.device, dtype=torch.float32)
-        else:
-            lout = torch.ones((gy.shape[0], gy.shape[1]), device=x.device, dtype=torch.float32)
+        try:
+            rc = _lib.load().ideas_conv3x3_wino_wgrad(_lib.ptr(gu), _lib.ptr(gy), _lib.ptr(x), _lib.ptr(lin), _lib.ptr(lout),
+                                                      C.byref(p), _lib.F32, _lib.stream_ptr())
+            _lib.check(rc, "ideas_conv3x3_wino_wgrad")
+            return _wino_fold(gu, out, co, ci, w_shape, x.device, clear=True)
+        except BaseException:
+            _GU.pop(key, None)            # the scratch may hold a partial dU that no fold cleared: the next call makes a fresh one
+            raise
     mfma = (L.Cin % 4 == 0) and (L.Cout % 4 == 0)       # the atomics-accumulating kernels
     if out is not None and mfma and tuple(out.shape) == tuple(w_shape) and out.is_contiguous(memory_format=CL):
         launch_wgrad(out, gy, x, L, gain, lin, lout)
@@ -414,96 +420,50 @@ def conv_wgrad_raw(gy, x, g: ConvGeom, w_shape, gain: float, lin=None, lout=None
 
 
 # ----------------------------------------------------------------------------------------------------
-# Gradient sink.  Inside ``with grad_sink(params):`` the weight gradients of those parameters are produced on a side
-# stream and accumulated straight into their (pre-existing, e.g. flat-bucket) ``.grad`` — the Functions return None
-# for the weight, so autograd neither allocates, zero-fills nor adds.  The weight-gradient kernels (MFMA-bound) then
-# overlap the HBM-bound elementwise backward passes of the following layers on the main stream.  Leaving the context
-# joins the side stream.  Only plain backward passes qualify (no create_graph), and only parameters named by the caller:
-# a Function cannot see the ``inputs=`` filter of ``torch.autograd.backward``.
-# ----------------------------------------------------------------------------------------------------
-_SINK = {"ids": None, "stream": None}
-# IDEAS_SINK_PRIORITY=low puts the side stream on the device's LOWEST priority (ideas_stream_create).  Measured round 5, same box,
-# interleaved: f32 412.2 -> 413.6 ms, bf16 154.7 -> 154.2 ms (noise) -- and the same with the whole iteration on a highest-priority
-# stream (414.2 ms).  A kernel trace shows 20-us torch adds of the main stream taking up to 1.9 ms next to a weight-gradient grid, but
-# the chip is busy throughout: the queue priority changes who waits, not how much work the compute units retire.  Default: off.
-SINK_LOW_PRIORITY = _os.environ.get("IDEAS_SINK_PRIORITY", "default") == "low"
-
-
-class grad_sink:
-    """``defer=True``: leaving the context does NOT join the side stream; the caller does (``join()``) before it consumes the
-    gradients.  The D phase's weight gradients are wanted only by the discriminators' optimiser step, which the step defers to the
-    first discriminator call of the G phase (train_step._Deferred) -- until then they may keep running under the generator
-    forwards of the G phase instead of holding the main stream at the end of the backward pass."""
-
-    def __init__(self, params, defer: bool = False):
-        self.ids = {id(p) for p in params if p.grad is not None and p.is_cuda}
-        self.defer = defer
-        self.pending = False
-
-    def __enter__(self):
-        if not self.ids:            # nothing to sink (no pre-existing device gradients): plain autograd
-            return self
-        if _SINK["stream"] is None:
-            _SINK["stream"] = _lib.make_stream(-1) if SINK_LOW_PRIORITY else torch.cuda.Stream()
-        _SINK["ids"] = self.ids
-        return self
-
-    def __exit__(self, *exc):
-        if _SINK["ids"] is not None:
-            _SINK["ids"] = None
-            if self.defer and exc[0] is None:
-                self.pending = True
-            else:
-                torch.cuda.current_stream().wait_stream(_SINK["stream"])
-
-    def join(self):
-        if self.pending:
-            self.pending = False
-            torch.cuda.current_stream().wait_stream(_SINK["stream"])
-
-
-def _sink_target(w: torch.Tensor):
-    ids = _SINK["ids"]
-    if ids is None or torch.is_grad_enabled():
-        return None
-    base = w._base if w._base is not None else w
-    if id(base) not in ids:
-        return None
-    gr = base.grad
-    if gr is None or gr.shape != base.shape or gr.stride() != base.stride():
-        return None
-    if base is w:
-        return gr
-    if w.numel() != base.numel() or w.data_ptr() != base.data_ptr():
-        return None
-    return gr.as_strided(w.shape, w.stride())
-
-
-_SIDE_STREAM = _os.environ.get("IDEAS_SIDE_STREAM", "1") != "0"
-
-
-def weight_grad(w: torch.Tensor, compute, *uses):
-    """``compute(out)`` -> the gradient of ``w`` (added to ``out`` when that is not None).  Returns it, or None after
-    sinking it into ``w.grad`` on the side stream (``uses``: the tensors the kernels read, for the allocator)."""
-    tgt = _sink_target(w)
-    if tgt is None:
-        return compute(None)
-    if not _SIDE_STREAM:                 # (A/B only: same in-place accumulation, on the current stream)
-        compute(tgt)
-        return None
-    side, cur = _SINK["stream"], torch.cuda.current_stream()
-    side.wait_stream(cur)
-    for t in uses:
-        if t is not None:
-            t.record_stream(side)
-    with torch.cuda.stream(side):
-        compute(tgt)
-    return None
-
-
-# ----------------------------------------------------------------------------------------------------
 # dense convolution with double backward
 # ----------------------------------------------------------------------------------------------------
+
+def _wgrad(w, gy, x, g: ConvGeom, gain: float):
+    """Weight gradient of a dense conv: differentiable Function normally, sunk into w.grad inside grad_sink."""
+    if _sink_target(w) is None:
+        return _ConvWgrad.apply(gy, x, g, gain, tuple(w.shape))
+    gy, x = _nhwc(gy), _nhwc(x)
+    return weight_grad(w, lambda out: conv_wgrad_raw(gy, x, g, tuple(w.shape), gain, out=out), gy, x)
+
+
+def _dense_backward(need_x: bool, need_w: bool, gy, x, w, g: ConvGeom, gain: float):
+    """(gx, gw) of y = gain * conv(x, w) for the cotangent ``gy``, each a differentiable Function (or None when not needed)."""
+    gx = _ConvDgrad.apply(gy, w, g, gain, (x.shape[2], x.shape[3])) if need_x else None
+    gw = _wgrad(w, gy, x, g, gain) if need_w else None
+    return gx, gw
+
+
+def _act_backward(gy, y, bias_ref, need_b: bool, slope: float, act_gain: float):
+    """Backward of y = lrelu(pre + bias) * act_gain from the saved ``y`` -> (gradient of pre, bias gradient to hand to autograd).
+    Inside grad_sink the kernel accumulates the bias gradient into bias.grad (None is returned for it); otherwise the differentiable
+    Function (a frozen layer -- the discriminators in the G phase -- needs no bias gradient: no zero-fill, no reduction in the kernel)."""
+    tgt = bias_sink(bias_ref) if need_b else None
+    if tgt is not None:
+        return bias_act_raw(gy, None, y, 1, slope, act_gain, bias_grad_into=tgt)[0], None
+    g_pre, gb = FusedLeakyReLUFunctionBackward.apply(gy, y, slope, act_gain, bool(need_b))
+    return g_pre, (gb if need_b else None)
+
+
+def _blur_act_backward(gyb, y1, fir, ctx, bias_ref, need_b: bool, slope: float, act_gain: float):
+    """Backward of upfirdn2d(y1, fir, ctx.pad4) with y1 = lrelu(pre + bias) * act_gain -> (gradient of pre, bias gradient for
+    autograd).  A plain pass: ONE kernel takes the blur's adjoint, applies the leaky-ReLU mask of the saved activation and reduces
+    the bias gradient (ideas_blur_fused; into bias.grad inside grad_sink).  When a graph is being built (R1's double backward), or
+    the kernel does not cover the shape: composed of the differentiable Functions."""
+    if torch.is_grad_enabled() or not blur_fused_ok(y1, fir):
+        g1 = UpFirDn2dBackward.apply(gyb, fir, (1, 1), (1, 1), ctx.pad4, ctx.g_pad, tuple(y1.shape), ctx.out_hw)
+        g_pre, gb = FusedLeakyReLUFunctionBackward.apply(g1, y1, slope, act_gain, bool(need_b))
+    else:
+        tgt = bias_sink(bias_ref) if need_b else None
+        gb = None if tgt is not None else torch.zeros(y1.shape[1], device=y1.device, dtype=torch.float32)
+        g_pre = blur_fused_raw(_nhwc(gyb), fir, ctx.g_pad, (y1.shape[2], y1.shape[3]), False, BLUR_ACT_BWD, ref=y1,
+                               bias_grad=tgt if tgt is not None else gb, alpha=slope, scale=act_gain)
+    return g_pre, (gb if need_b else None)
+
 
 class _Conv(Function):
     """y = gain * conv(x, w).  backward -> _ConvDgrad / _ConvWgrad (both differentiable)."""
@@ -518,12 +478,7 @@ class _Conv(Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = _ConvDgrad.apply(gy, w, ctx.g, ctx.gain, (x.shape[2], x.shape[3]))
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad(w, gy, x, ctx.g, ctx.gain)
-        return gx, gw, None, None
+        return (*_dense_backward(ctx.needs_input_grad[0], ctx.needs_input_grad[1], gy, x, w, ctx.g, ctx.gain), None, None)
 
 
 class _ConvAdd(Function):
@@ -540,20 +495,8 @@ class _ConvAdd(Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = _ConvDgrad.apply(gy, w, ctx.g, ctx.gain, (x.shape[2], x.shape[3]))
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad(w, gy, x, ctx.g, ctx.gain)
-        return gx, gw, (gy if ctx.needs_input_grad[2] else None), None, None
-
-
-def _wgrad(w, gy, x, g: ConvGeom, gain: float):
-    """Weight gradient of a dense conv: differentiable Function normally, sunk into w.grad inside grad_sink."""
-    if _sink_target(w) is None:
-        return _ConvWgrad.apply(gy, x, g, gain, tuple(w.shape))
-    gy, x = _nhwc(gy), _nhwc(x)
-    return weight_grad(w, lambda out: conv_wgrad_raw(gy, x, g, tuple(w.shape), gain, out=out), gy, x)
+        need = ctx.needs_input_grad
+        return (*_dense_backward(need[0], need[1], gy, x, w, ctx.g, ctx.gain), (gy if need[2] else None), None, None)
 
 
 class _ConvDgrad(Function):
@@ -616,15 +559,13 @@ class _ForkConv(Function):
         x, w = ctx.saved_tensors
         if gh is None:
             return ga, None, None, None
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            if ga is not None and not torch.is_grad_enabled() and ga.is_contiguous(memory_format=CL) and ga.dtype == x.dtype:
-                gx = conv_dgrad_raw(_nhwc(gh), w, ctx.g, (x.shape[2], x.shape[3]), ctx.gain, resid=ga)
-            else:
-                gx = _ConvDgrad.apply(gh, w, ctx.g, ctx.gain, (x.shape[2], x.shape[3]))
-                gx = gx if ga is None else gx + ga
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad(w, gh, x, ctx.g, ctx.gain)
+        need = ctx.needs_input_grad
+        if need[0] and ga is not None and not torch.is_grad_enabled() and ga.is_contiguous(memory_format=CL) and ga.dtype == x.dtype:
+            gx = conv_dgrad_raw(_nhwc(gh), w, ctx.g, (x.shape[2], x.shape[3]), ctx.gain, resid=ga)
+            gw = _dense_backward(False, need[1], gh, x, w, ctx.g, ctx.gain)[1]
+        else:
+            gx, gw = _dense_backward(need[0], need[1], gh, x, w, ctx.g, ctx.gain)
+            gx = gx if (gx is None or ga is None) else gx + ga
         return gx, gw, None, None
 
 
@@ -634,9 +575,6 @@ def fork_conv2d(input: torch.Tensor, weight: torch.Tensor, padding: int = 0, gai
     _lib.require_cuda(input, weight)
     g = ConvGeom(weight.shape[2], weight.shape[3], 1, padding, False)
     return _ForkConv.apply(to_act(input), weight, g, float(gain))
-
-
-_BIAS_SUM_HIP = _os.environ.get("IDEAS_BIAS_SUM_HIP", "1") != "0"      # 0: autograd's composite sum (A/B only)
 
 
 class _AddBias(Function):
@@ -658,7 +596,6 @@ class _AddBias(Function):
             if torch.is_grad_enabled() or not _BIAS_SUM_HIP:
                 gb = gy.sum((0, 2, 3)).to(ctx.bias_ref.dtype)
             else:
-                from .fused_act import bias_sink, channel_sum
                 tgt = bias_sink(ctx.bias_ref)
                 gb = channel_sum(gy, into=tgt)
                 gb = None if gb is None else gb.to(ctx.bias_ref.dtype)
@@ -697,21 +634,10 @@ class _ConvBiasAct(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .fused_act import FusedLeakyReLUFunctionBackward
         x, w, y = ctx.saved_tensors
-        from .fused_act import bias_act_raw, bias_sink
-        tgt = bias_sink(ctx.bias_ref) if ctx.needs_input_grad[2] else None
-        if tgt is not None:          # gradient sink: bias gradient accumulated by the kernel into bias.grad
-            g_pre, gb = bias_act_raw(gy, None, y, 1, ctx.slope, ctx.act_gain, bias_grad_into=tgt)
-        else:
-            # (a frozen layer -- the discriminators in the G phase -- needs no bias gradient: no zero-fill, no reduction in the kernel)
-            g_pre, gb = FusedLeakyReLUFunctionBackward.apply(gy, y, ctx.slope, ctx.act_gain, bool(ctx.needs_input_grad[2]))
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = _ConvDgrad.apply(g_pre, w, ctx.g, ctx.gain, (x.shape[2], x.shape[3]))
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad(w, g_pre, x, ctx.g, ctx.gain)
-        return gx, gw, (gb if (ctx.needs_input_grad[2] and tgt is None) else None), None, None, None, None
+        need = ctx.needs_input_grad
+        g_pre, gb = _act_backward(gy, y, ctx.bias_ref, need[2], ctx.slope, ctx.act_gain)
+        return (*_dense_backward(need[0], need[1], g_pre, x, w, ctx.g, ctx.gain), gb, None, None, None, None)
 
 
 class _ConvBiasActBlur(Function):
@@ -723,7 +649,6 @@ class _ConvBiasActBlur(Function):
 
     @staticmethod
     def forward(ctx, x, w, b, g: ConvGeom, gain: float, slope: float, act_gain: float, fir, pad2):
-        from .upfirdn2d import blur_geometry, upfirdn2d_raw
         x = _nhwc(x)
         y1 = conv_fwd_raw(x, w, g, gain, bias=b.contiguous(), act=True, act_gain=act_gain, alpha=slope)
         pad4, out_hw, g_pad = blur_geometry((y1.shape[2], y1.shape[3]), fir, pad2)
@@ -736,36 +661,15 @@ class _ConvBiasActBlur(Function):
 
     @staticmethod
     def backward(ctx, gyb):
-        from .fused_act import FusedLeakyReLUFunctionBackward, bias_sink
-        from .upfirdn2d import BLUR_ACT_BWD, UpFirDn2dBackward, blur_fused_ok, blur_fused_raw
         x, w, y1, fir = ctx.saved_tensors
-        need_b = ctx.needs_input_grad[2]
-        gb = None
-        if torch.is_grad_enabled() or not blur_fused_ok(y1, fir):
-            g1 = UpFirDn2dBackward.apply(gyb, fir, (1, 1), (1, 1), ctx.pad4, ctx.g_pad, tuple(y1.shape), ctx.out_hw)
-            g_pre, gb = FusedLeakyReLUFunctionBackward.apply(g1, y1, ctx.slope, ctx.act_gain, bool(need_b))
-        else:
-            tgt = bias_sink(ctx.bias_ref) if need_b else None
-            if tgt is None:
-                gb = torch.zeros(y1.shape[1], device=y1.device, dtype=torch.float32)
-            g_pre = blur_fused_raw(_nhwc(gyb), fir, ctx.g_pad, (y1.shape[2], y1.shape[3]), False, BLUR_ACT_BWD, ref=y1,
-                                   bias_grad=tgt if tgt is not None else gb, alpha=ctx.slope, scale=ctx.act_gain)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = _ConvDgrad.apply(g_pre, w, ctx.g, ctx.gain, (x.shape[2], x.shape[3]))
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad(w, g_pre, x, ctx.g, ctx.gain)
-        return gx, gw, (gb if need_b else None), None, None, None, None, None, None
+        need = ctx.needs_input_grad
+        g_pre, gb = _blur_act_backward(gyb, y1, fir, ctx, ctx.bias_ref, need[2], ctx.slope, ctx.act_gain)
+        return (*_dense_backward(need[0], need[1], g_pre, x, w, ctx.g, ctx.gain), gb, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------------------
-# Blur -> 3x3 / stride-2 conv (+ bias + leaky-ReLU) of a downsampling ConvLayer in ONE kernel (csrc/conv_b3_s2fir.hip): the
-# blurred tensor is built in LDS under each output patch and never makes the round trip through HBM.  IDEAS_BLUR_CONV=0 keeps the
-# blur a separate pass (A/B measurements).
+# Blur -> 3x3 / stride-2 conv (+ bias + leaky-ReLU) of a downsampling ConvLayer in ONE kernel (BLUR_CONV, csrc/conv_b3_s2fir.hip)
 # ----------------------------------------------------------------------------------------------------
-BLUR_CONV = _os.environ.get("IDEAS_BLUR_CONV", "1") != "0"
-BLUR_CONV_MIN_OW = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_OW", "16"))      # below: the 8 x 16 output patch of the kernel would idle
-BLUR_CONV_MIN_BLOCKS = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_BLOCKS", "512"))   # down_pair_ok: below, the two-kernel chain wins
 
 
 def fir_factors(fir: torch.Tensor, flip: bool = True):
@@ -852,7 +756,6 @@ class _DownPair(Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, g1: ConvGeom, gain1: float, slope1: float, ag1: float, fir, pad2, gain2: float,
                 slope2: float, ag2: float):
-        from .upfirdn2d import blur_geometry
         x = _nhwc(x)
         y1 = conv_fwd_raw(x, w1, g1, gain1, bias=b1.contiguous(), act=True, act_gain=ag1, alpha=slope1)
         need_xb = ctx.needs_input_grad[3]
@@ -867,40 +770,15 @@ class _DownPair(Function):
 
     @staticmethod
     def backward(ctx, gy2):
-        from .fused_act import FusedLeakyReLUFunctionBackward, bias_act_raw, bias_sink
-        from .upfirdn2d import BLUR_ACT_BWD, UpFirDn2dBackward, blur_fused_ok, blur_fused_raw, upfirdn2d_raw
-        x, w1, y1, w2, y2, fir, yb = ctx.saved_tensors
+        x, w1, y1, w2, y2, fir, yb = ctx.saved_tensors      # (yb: the conv kernel's side output, written iff w2 needed a gradient)
         need = ctx.needs_input_grad
+        g_pre2, gb2 = _act_backward(gy2, y2, ctx.b2_ref, need[4], ctx.slope2, ctx.ag2)
         g2 = ConvGeom(3, 3, 2, 0, False)
-        gb1 = gb2 = None
-        tgt2 = bias_sink(ctx.b2_ref) if need[4] else None
-        if tgt2 is not None:
-            g_pre2, _ = bias_act_raw(gy2, None, y2, 1, ctx.slope2, ctx.ag2, bias_grad_into=tgt2)
-        else:
-            g_pre2, gb2 = FusedLeakyReLUFunctionBackward.apply(gy2, y2, ctx.slope2, ctx.ag2, bool(need[4]))
-        gw2 = None
-        if need[3]:
-            if yb is None:      # (cannot happen: w2 required a gradient in the forward, so the side output was written)
-                yb = upfirdn2d_raw(y1, fir, (1, 1), (1, 1), ctx.pad4, ctx.out_hw, flip=True)
-            gw2 = _wgrad(w2, g_pre2, yb, g2, ctx.gain2)
+        gw2 = _wgrad(w2, g_pre2, yb, g2, ctx.gain2) if need[3] else None
         gyb = _ConvDgrad.apply(g_pre2, w2, g2, ctx.gain2, ctx.out_hw)
-        if torch.is_grad_enabled() or not blur_fused_ok(y1, fir):
-            g1 = UpFirDn2dBackward.apply(gyb, fir, (1, 1), (1, 1), ctx.pad4, ctx.g_pad, tuple(y1.shape), ctx.out_hw)
-            g_pre1, gb1 = FusedLeakyReLUFunctionBackward.apply(g1, y1, ctx.slope1, ctx.ag1, bool(need[2]))
-        else:
-            tgt1 = bias_sink(ctx.b1_ref) if need[2] else None
-            if tgt1 is None:
-                gb1 = torch.zeros(y1.shape[1], device=y1.device, dtype=torch.float32)
-            g_pre1 = blur_fused_raw(_nhwc(gyb), fir, ctx.g_pad, (y1.shape[2], y1.shape[3]), False, BLUR_ACT_BWD, ref=y1,
-                                    bias_grad=tgt1 if tgt1 is not None else gb1, alpha=ctx.slope1, scale=ctx.ag1)
-            if tgt1 is not None:
-                gb1 = None
-        gx = gw1 = None
-        if need[0]:
-            gx = _ConvDgrad.apply(g_pre1, w1, ctx.g1, ctx.gain1, (x.shape[2], x.shape[3]))
-        if need[1]:
-            gw1 = _wgrad(w1, g_pre1, x, ctx.g1, ctx.gain1)
-        return (gx, gw1, (gb1 if need[2] else None), gw2, (gb2 if (need[4] and tgt2 is None) else None),
+        g_pre1, gb1 = _blur_act_backward(gyb, y1, fir, ctx, ctx.b1_ref, need[2], ctx.slope1, ctx.ag1)
+        gx, gw1 = _dense_backward(need[0], need[1], g_pre1, x, w1, ctx.g1, ctx.gain1)
+        return (gx, gw1, gb1, gw2, gb2,
                 None, None, None, None, None, None, None, None, None)
 
 
@@ -908,7 +786,6 @@ def down_pair_ok(input: torch.Tensor, w1, w2, fir, pad2, padding1: int = 1) -> b
     """Shapes / precision ``down_pair`` covers: f32 activations (the bf16 path keeps its own kernels), the split-bf16 contraction,
     a separable 4x4 FIR, >= 8 x 16 output pixels per image, Cin % 16 == 0; with a weight gradient pending also the blurred size
     2 OH + 1 (every blurred pixel is then written by the conv kernel's side output)."""
-    from ..precision import activation_dtype
     if not input.is_cuda or activation_dtype() != torch.float32 or input.dim() != 4:
         return False
     g1 = ConvGeom(w1.shape[2], w1.shape[3], 1, padding1, False)

@@ -102,6 +102,7 @@ _RECORDED = {}      # cache key -> (prep, weakref of the base parameter, its dat
 _PREP_STATE = {}    # tuple of cache keys -> per-op launch state (device table, blocks, persistent outputs)
 _KEYS_OF = {}       # (span set (None = everything), precision) -> the sorted tuple of recorded keys inside it
 _OUT_BUF = {}       # cache key -> its persistent destination buffer, shared by every span selection that contains the key
+_DEPS = {}          # cache key -> addresses of further parameters the entry was derived from (cached_on(..., deps=...))
 
 
 def _prep_state(keys):
@@ -188,6 +189,7 @@ def _prefill(spans=None) -> None:
 def cache_begin() -> None:
     global _CACHE
     _CACHE = {}
+    _DEPS.clear()
     _prefill(None)
 
 
@@ -229,6 +231,7 @@ def cache_clear(params=None, refill: bool = True) -> None:
 def cache_end() -> None:
     global _CACHE
     _CACHE = None
+    _DEPS.clear()           # (keyed like _CACHE: an entry must not outlive the cache it describes)
 
 
 def cached(w: torch.Tensor, key, make, prep=None):
@@ -282,9 +285,6 @@ def _budget_admit(k, nbytes: int) -> bool:
     BUDGET_STATS["admitted"] += 1
     BUDGET_STATS["peak_bytes"] = max(BUDGET_STATS["peak_bytes"], _BUDGET_TOTAL[0])
     return True
-
-
-_DEPS = {}          # cache key -> addresses of further parameters the entry was derived from (cached_on(..., deps=...))
 
 
 def cached_on(w: torch.Tensor, key, t: torch.Tensor, make, budget: bool = False, deps=()):

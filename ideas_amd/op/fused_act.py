@@ -18,6 +18,7 @@ from torch import nn
 from torch.autograd import Function
 
 from .. import _lib
+from .grad_sink import _sink_target
 
 
 def _layout_of(x: torch.Tensor):
@@ -116,10 +117,9 @@ def channel_sum(x: torch.Tensor, into: Optional[torch.Tensor] = None) -> Optiona
 
 
 def bias_sink(bias: Optional[torch.Tensor]):
-    """Inside ``grad_sink`` (op/conv.py) and a plain backward: the bias parameter's gradient buffer to accumulate into."""
+    """Inside ``grad_sink`` (op/grad_sink.py) and a plain backward: the bias parameter's gradient buffer to accumulate into."""
     if bias is None:
         return None
-    from .conv import _sink_target
     tgt = _sink_target(bias)
     return tgt if (tgt is not None and tgt.dim() == 1 and tgt.is_contiguous() and tgt.dtype == torch.float32) else None
 

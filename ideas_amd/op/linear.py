@@ -8,7 +8,7 @@ layers that share their input:
 * ``multi_linear``   L layers applied to the same input as ONE autograd node -- the generator's sixteen modulation layers
   (stylegan2/model.py:226,239, all fed the same texture code): one launch forward, and in the backward one launch for the SUM of the
   sixteen input gradients (what autograd would otherwise add up in fifteen passes) and one for the sixteen weight + bias gradients,
-  which inside ``grad_sink`` (op/conv.py) accumulate straight into the parameters' pre-existing ``.grad``.
+  which inside ``grad_sink`` (op/grad_sink.py) accumulate straight into the parameters' pre-existing ``.grad``.
 
 The equalised-lr scale rides in the kernels (no scaled copy of the weight).  Under ``create_graph`` (R1 through the discriminator
 heads, the path-length regulariser through the modulation layers) and for shapes the kernels do not take (K % 8, N % 8 for the input
@@ -23,7 +23,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from .conv import _sink_target
+from .grad_sink import _sink_target
 
 LINEAR_HIP = True      # (tests flip this to compare the HIP kernels with the library-GEMM form the odd shapes below still take)
 

@@ -24,12 +24,13 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..precision import to_act, to_f32
-from .conv import conv_dgrad_raw, conv_fwd_raw, conv_wgrad_raw, weight_grad, _nhwc
+from .conv import conv2d, conv_dgrad_raw, conv_fwd_raw, conv_transpose2d, conv_wgrad_raw, _nhwc
 from .conv_plan import ConvGeom, convT_out_size
 from . import conv_plan
 from . import scratch
 from .upfirdn2d import blur_bias_act, upfirdn2d
-from .fused_act import fused_leaky_relu
+from .fused_act import bias_sink, fused_leaky_relu
+from .grad_sink import weight_grad
 
 
 def pixel_dot(a: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
@@ -223,7 +224,6 @@ class _ModConvAct(Function):
         x, w, s, d, b, y = ctx.saved_tensors
         g, gain = ctx.g, ctx.gain
         need_x, need_w, need_s, need_b = ctx.needs_input_grad[:4]
-        from .fused_act import bias_sink
         gpre, gb, dot_d = act_bwd_dot(gy, y, b, ctx.slope, ctx.act_gain, bias_grad_into=bias_sink(ctx.bias_ref) if need_b else None)
         gx = gw = gs = gq = None
         if need_x or need_s:
@@ -259,7 +259,6 @@ class second_order:
 
 
 def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale):
-    from .conv import conv2d, conv_transpose2d
     cout, cin, k, _ = w.shape
     scale = 1.0 / math.sqrt(cin * k * k)
     xs = x * style.view(style.shape[0], cin, 1, 1)

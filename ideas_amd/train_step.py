@@ -31,7 +31,7 @@ from torch import optim
 from torch.nn import functional as F
 
 from .op import conv_plan, scratch
-from .op.conv import grad_sink
+from .op.grad_sink import grad_sink
 from .utils import (Box, accumulate, d_logistic_loss, d_r1_loss, draw_boxes, g_nonsaturating_loss,
                     message_to_tensor, patchify_image, requires_grad, tensor_to_message)
 
@@ -45,7 +45,7 @@ import os as _os
 # box, two interleaved runs (profiles/r06_g_pair_ab.txt): 395.6 -> 393.5 ms f32, 147.2 -> 146.4 bf16; pairing the D phase's two no-grad
 # passes as well changes nothing ("d": 395.7 / 147.5).  IDEAS_G_PAIR=x: separate passes (A/B); "dg": both phases.
 _G_PAIR = _os.environ.get("IDEAS_G_PAIR", "g")
-DEFER_SINK_JOIN = _os.environ.get("IDEAS_DEFER_SINK_JOIN", "1") != "0"     # A/B switch (see op/conv.py::grad_sink)
+DEFER_SINK_JOIN = _os.environ.get("IDEAS_DEFER_SINK_JOIN", "1") != "0"     # A/B switch (see op/grad_sink.py)
 EMA_NETS = ("E", "G", "Gstru", "Ex")
 G_SIDE = ("E", "G", "Gstru")
 D_SIDE = ("Dreal", "Dco", "Ddist")

@@ -541,3 +541,81 @@ def test_conv_bias_call_sites_are_the_rgb_head_only():
             if isinstance(m, (EqualConv2d, EqualConvTranspose2d)) and m.bias is not None:
                 sites.append(f"{tag}.{name}")
     assert sites == ["G.to_rgb.0"], sites
+
+
+def test_wino_weight_gradient_scratch_is_dropped_when_a_launch_fails(monkeypatch):
+    """op.conv._GU keeps ONE zeroed dU scratch per (stream, size), re-zeroed only by the fold that follows the Winograd
+    weight-gradient launch.  If that launch or the fold fails, nothing has cleared what was accumulated: the entry must leave _GU,
+    so that the next weight gradient of that size starts from a fresh zeroed buffer instead of adding to the leftovers."""
+    from ideas_amd import _lib
+    from ideas_amd.op import conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom
+
+    class Lib:
+        fail = None
+        seen = []
+
+        def ideas_conv3x3_wino_wgrad(self, gu, *rest):
+            (buf,) = [b for b in CV._GU.values() if b.data_ptr() == gu]
+            self.seen.append(buf.clone())
+            buf.fill_(1.0)                                   # the kernel accumulates dU into the scratch
+            return 1 if self.fail == "wgrad" else 0
+
+        def ideas_wino_wgrad_fold(self, tgt, gu, *rest):
+            if self.fail == "fold":
+                return 1
+            (buf,) = [b for b in CV._GU.values() if b.data_ptr() == gu]
+            buf.zero_()                                      # clear = 1: re-zeroed behind the read
+            return 0
+
+        def ideas_strerror(self, rc):
+            return b"injected failure"
+
+    lib = Lib()
+    monkeypatch.setattr(_lib, "load", lambda: lib)
+    monkeypatch.setattr(_lib, "stream_ptr", lambda: 0)
+    monkeypatch.setattr(CV, "_GU", {})
+    monkeypatch.setattr(CV, "MATH", _lib.F32)
+    monkeypatch.setattr(CV, "WINOGRAD", True)
+    g = ConvGeom(3, 3, 1, 1, False)
+    x, gy = torch.randn(1, 8, 4, 4), torch.randn(1, 4, 4, 4)
+
+    def run():
+        return CV.conv_wgrad_raw(gy, x, g, (4, 8, 3, 3), 1.0)
+    for stage in ("wgrad", "fold"):
+        lib.fail = stage
+        with pytest.raises(RuntimeError, match="injected failure"):
+            run()
+        assert CV._GU == {}, f"dirty scratch kept after a failing {stage}"
+        lib.fail = None
+        run()
+        assert not lib.seen[-1].any(), f"the launch after a failing {stage} was handed a dirty scratch"
+        (buf,) = CV._GU.values()
+        assert not buf.any()
+        run()                                                # and a good call keeps (and reuses) its scratch
+        assert list(CV._GU.values())[0] is buf and not lib.seen[-1].any()
+        CV._GU.clear()
+
+
+def test_cache_cycle_leaves_no_dependency_records(monkeypatch):
+    """conv_plan._DEPS (cache key -> further parameters an entry derives from) is keyed like _CACHE and must not outlive
+    it: a cache_begin / cache_end cycle leaves it empty, and a new cycle does not start with the last one's records."""
+    from ideas_amd.op import conv_plan as P
+    monkeypatch.setattr(P, "PREFILL", False)
+    w, dep = torch.nn.Parameter(torch.randn(4, 4)), torch.nn.Parameter(torch.randn(4))
+    t = torch.randn(2, 4)
+    assert P._CACHE is None and not P._DEPS
+    P.cache_begin()
+    try:
+        P.cached_on(w, ("k",), t, lambda: w.detach() * 2, deps=(dep,))
+        assert list(P._DEPS.values()) == [(dep.data_ptr(),)]
+    finally:
+        P.cache_end()
+    assert not P._DEPS
+    P._DEPS[("left over",)] = (dep.data_ptr(),)              # (whatever put it there)
+    P.cache_begin()
+    try:
+        assert not P._DEPS
+    finally:
+        P.cache_end()
+    assert not P._DEPS

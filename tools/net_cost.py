@@ -13,7 +13,7 @@ CL = torch.channels_last
 
 
 from ideas_amd.op import conv_plan
-from ideas_amd.op.conv import grad_sink
+from ideas_amd.op.grad_sink import grad_sink
 CUR = {"net": None}
 
 
@@ -28,7 +28,7 @@ def run(fn, n):
 def timeit(name, fn, flops_gf, n=3):
     """Two figures: plain autograd (.backward() allocating, zero-filling and summing every weight gradient, the derived weights
     remade by every call), and the way train_iteration runs the network: derived-weight cache on, weight gradients sunk into the
-    pre-existing .grad buffers on the side stream (op/conv.py::grad_sink)."""
+    pre-existing .grad buffers on the side stream (op/grad_sink.py)."""
     ms = run(fn, n)
     params = list(nets[CUR["net"]].parameters())
     for q in params:

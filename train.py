@@ -160,7 +160,7 @@ def main():
             with open(f"{base_dir}/training_logs.txt", "a") as fp:
                 fp.write(line + "\n")
 
-        if iter_idx % args.show_every == 0 and rank == 0:              # train.py:249-293 (test block; no image grid)
+        if iter_idx % args.show_every == 0 and rank == 0:              # train.py:249-303 (test block + image grid)
             with torch.no_grad():
                 s = args.image_size // 16
                 M = torch.randint(low=0, high=2, dtype=torch.float, size=(X.shape[0], args.N * s * s))

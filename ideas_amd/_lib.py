@@ -109,6 +109,8 @@ _PROTOS = {
     "ideas_b3_blur_conv_s2_supported": (C.c_int, [C.POINTER(ConvParams), C.c_int, C.c_int, C.c_int]),
     "ideas_b3_blur_conv_s2": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, C.POINTER(ConvParams),
                                         C.c_int, C.c_int, C.c_int, _P]),
+    "ideas_b3_blur_conv_s2_mod": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P,
+                                            C.POINTER(ConvParams), C.c_int, C.c_int, C.c_int, _P]),
     "ideas_conv_direct": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(ConvParams), C.c_int, _P]),
     "ideas_conv_wgrad": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ConvParams), C.c_int, _P]),
     "ideas_conv_wgrad_direct": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ConvParams), C.c_int, _P]),

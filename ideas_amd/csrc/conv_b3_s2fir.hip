@@ -71,7 +71,12 @@ constexpr int NPW = 4;                         // producer (FIR) waves: one per 
 // order of conv_b3_kernel).  The generic kernel stages every input pixel once per TAP (nine times: 195-203 TFLOP/s on the input
 // gradients of G's upsampling layers); here it is staged once per chunk for all nine, and the consumer side is the one that runs
 // 297-304 TFLOP/s when nothing else is in its way.
-template <int NCW, int WN, int NB, bool XBOUT, int MODE = 0>
+// MOD (MODE 0 only): the blur + stride-2 conv of a downsampling ModulatedConv2d (stylegan2/model.py:210-216, 263-269): the producers
+// multiply the blurred f32 value by in_scale[b, ci] (one rounding, BEFORE the split: the staged value is bitwise s * blur4_f32_c2(x),
+// what the scaled stride-2 kernels stage behind a stand-alone blur pass), the epilogue multiplies by out_scale[b, o] where
+// conv_b3_kernel and MODE 1 do; the side output stays the UNSCALED blurred tensor (the weight gradient applies the scale itself).  A
+// template parameter, not a branch in the row loop: the unmodulated instantiations compile to what they compiled to without it.
+template <int NCW, int WN, int NB, bool XBOUT, int MODE = 0, bool MOD = false>
 __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(float* __restrict__ y, float* __restrict__ xb_out,
                                                                const float* __restrict__ x, const void* __restrict__ wplanes,
                                                                const float* __restrict__ bias, const float* __restrict__ resid,
@@ -182,11 +187,16 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
             return fmaf(r3, f.kv[3], s_);
         };
         // image row i (raw rows i .. i + 3 filtered): vertical sum, split, LDS store (+ side output)
-        auto emit = [&](unsigned char* buf, int i, int ci_chunk) {
+        auto emit = [&](unsigned char* buf, int i, int ci_chunk, float4 sc) {
             const float4 &r0 = h[i % 4], &r1 = h[(i + 1) % 4], &r2 = h[(i + 2) % 4], &r3 = h[(i + 3) % 4];
             const float4 o = make_float4(vsum1(r0.x, r1.x, r2.x, r3.x), vsum1(r0.y, r1.y, r2.y, r3.y), vsum1(r0.z, r1.z, r2.z, r3.z),
                                          vsum1(r0.w, r1.w, r2.w, r3.w));
-            const Split4 s_ = split4(o);
+            Split4 s_;
+            if constexpr (MOD) {                         // (in_scale is uniform: no divergence)
+                s_ = split4(in_scale ? make_float4(mul_rn(o.x, sc.x), mul_rn(o.y, sc.y), mul_rn(o.z, sc.z), mul_rn(o.w, sc.w)) : o);
+            } else {
+                s_ = split4(o);
+            }
             if (on) {                                    // (only the stores are conditional: no value is defined on one path only)
                 unsigned char* a = buf + ((i & 1) ? (w0 ^ 16) : w0) + i * PITCH * ROWB;
 #pragma unroll
@@ -205,7 +215,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
         };
 
         // MODE 1: image row i = input row i: scale (rounded to f32 before the split, as conv_b3_kernel does), split, store
-        const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)in_scale, 0, (MODE == 1 && in_scale) ? p.B * p.Cin * 4 : 0, (int)RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)in_scale, 0, ((MODE == 1 || MOD) && in_scale) ? p.B * p.Cin * 4 : 0, (int)RSRC_FLAGS);
         auto emit_plain = [&](unsigned char* buf, int i, float4 sc) {
             float4 v = ldv[i % RING];
             if (in_scale) v = make_float4(mul_rn(v.x, sc.x), mul_rn(v.y, sc.y), mul_rn(v.z, sc.z), mul_rn(v.w, sc.w));
@@ -226,13 +236,15 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
             asm volatile("" : "+v"(gbase), "+v"(rbad), "+v"(w0));
             if (XBOUT) asm volatile("" : "+v"(xb_off));
             if constexpr (MODE == 0) {
+                float4 sc = make_float4(1.f, 1.f, 1.f, 1.f);       // (MOD: the chunk's 4 scales of this lane's channel quad, once per chunk)
+                if constexpr (MOD) { if (in_scale) sc = buffer_load4(rsi, (unsigned)(pb * p.Cin + ci + quad * 4) * 4u, 0); }
 #pragma unroll
                 for (int r = 0; r < RAWR; ++r) {
                     if (S2FIR_ABL == 1) break;
                     if (S2FIR_ABL != 3) { if (r + AHEAD < RAWR) gload(r + AHEAD, ci); else gload(r + AHEAD - RAWR, ci_next); }
                     SB;
                     hrow(r);
-                    if (r >= 3) emit(buf, r - 3, ci);
+                    if (r >= 3) emit(buf, r - 3, ci, sc);
                     SB;
                 }
             } else {
@@ -349,7 +361,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
         const int n = n0 + (wn * NB + nb) * 32 + li;
         if (n >= p.Cout) continue;
         const float bv = bias ? bias[n] : 0.f;
-        const float osv = (MODE == 1 && out_scale) ? out_scale[(int64_t)pb * p.Cout + n] : 1.f;
+        const float osv = ((MODE == 1 || MOD) && out_scale) ? out_scale[(int64_t)pb * p.Cout + n] : 1.f;
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -359,7 +371,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
                 if (oy >= p.OH || ox >= p.OW) continue;
                 const int64_t off = (((int64_t)pb * p.YH + oy) * p.YW + ox) * p.Cout + n;
                 float v = mul_rn(acc[rb][nb][e], p.gain);
-                if (MODE == 1 && out_scale) v = mul_rn(v, osv);
+                if ((MODE == 1 || MOD) && out_scale) v = mul_rn(v, osv);
                 v = mul_then_add(v, 1.0f, bv);
                 if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
                 if (resid) v = (v + resid[off]) * p.resid_gain;
@@ -368,9 +380,9 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
     }
 }
 
-template <int NCW, int WN, int NB>
+template <int NCW, int WN, int NB, bool MOD = false>
 int launch_s2fir(void* y, void* xb, const void* x, const void* wplanes, const float* bias, const void* resid, const ideas_conv_params* p,
-                 const S2Fir& f, hipStream_t stream) {
+                 const S2Fir& f, hipStream_t stream, const float* in_scale = nullptr, const float* out_scale = nullptr) {
     constexpr int BN = WN * NB * 32;
     const int64_t tm = (int64_t)p->B * ideas_cdiv(p->OH, TR) * ideas_cdiv(p->OW, TP);
     const int tn = (int)ideas_cdiv(p->Cout, BN);
@@ -379,13 +391,11 @@ int launch_s2fir(void* y, void* xb, const void* x, const void* wplanes, const fl
     const unsigned xb_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
     const unsigned plane_bytes = (unsigned)((int64_t)9 * p->Cin * p->Cout * 2);
     if (xb)
-        hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, true>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)xb,
-                           (const float*)x, wplanes, bias, (const float*)resid, *p, f, tn, x_bytes, plane_bytes, xb_bytes, (const float*)nullptr,
-                           (const float*)nullptr);
+        hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, true, 0, MOD>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)xb,
+                           (const float*)x, wplanes, bias, (const float*)resid, *p, f, tn, x_bytes, plane_bytes, xb_bytes, in_scale, out_scale);
     else
-        hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, false>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)xb,
-                           (const float*)x, wplanes, bias, (const float*)resid, *p, f, tn, x_bytes, plane_bytes, xb_bytes, (const float*)nullptr,
-                           (const float*)nullptr);
+        hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, false, 0, MOD>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)xb,
+                           (const float*)x, wplanes, bias, (const float*)resid, *p, f, tn, x_bytes, plane_bytes, xb_bytes, in_scale, out_scale);
     return ideas_launch_status();
 }
 
@@ -422,12 +432,16 @@ extern "C" int ideas_b3_blur_conv_s2_supported(const ideas_conv_params* p, int x
            (int64_t)9 * p->Cin * p->Cout * 6 < 0xffffffffLL;
 }
 
-extern "C" int ideas_b3_blur_conv_s2(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v,
-                                     const float* bias, const void* resid, const ideas_conv_params* p, int xh, int xw, int pad0,
-                                     void* stream_) {
+namespace {
+
+template <bool MOD>
+int blur_conv_s2(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v, const float* in_scale,
+                 const float* out_scale, const float* bias, const void* resid, const ideas_conv_params* p, int xh, int xw, int pad0,
+                 void* stream_) {
     if (!y || !x || !wplanes || !fir_h || !fir_v || !p) return IDEAS_E_NULL;
     if (!ideas_b3_blur_conv_s2_supported(p, xh, xw, pad0)) return IDEAS_E_UNSUPPORTED;
     if (!ideas_aligned16(x) || !ideas_aligned16(wplanes) || (xb_out && !ideas_aligned16(xb_out))) return IDEAS_E_ALIGN;
+    if (MOD && in_scale && !ideas_aligned16(in_scale)) return IDEAS_E_ALIGN;     // (16-byte loads of four scales; Cin % 16 == 0)
     // the side output is complete only when every blurred pixel lies under an output pixel's taps (the 2 OH + 1 rows of an even input)
     if (xb_out && (p->IH != 2 * p->OH + 1 || p->IW != 2 * p->OW + 1)) return IDEAS_E_UNSUPPORTED;
     S2Fir f;
@@ -439,11 +453,29 @@ extern "C" int ideas_b3_blur_conv_s2(void* y, void* xb_out, const void* x, const
     const int cfg = ecfg ? atoi(ecfg) : 0;
     const bool eight = cfg == 1 || (cfg == 0 && p->Cout > 128);
     // a consumer wave = all 128 pixels x 32 channels (every weight fragment is loaded by exactly one wave)
-    if (p->Cout > 128 && eight) return launch_s2fir<8, 8, 1>(y, xb_out, x, wplanes, bias, resid, p, f, stream);   // N tile 256
-    if (p->Cout > 64) return eight ? launch_s2fir<8, 4, 1>(y, xb_out, x, wplanes, bias, resid, p, f, stream)     // 128: 2 x 4 waves of 64 x 32
-                                   : launch_s2fir<4, 4, 1>(y, xb_out, x, wplanes, bias, resid, p, f, stream);    //      1 x 4 waves of 128 x 32
-    return eight ? launch_s2fir<8, 2, 1>(y, xb_out, x, wplanes, bias, resid, p, f, stream)                       // 64:  4 x 2 waves of 32 x 32
-                 : launch_s2fir<4, 2, 1>(y, xb_out, x, wplanes, bias, resid, p, f, stream);                      //      2 x 2 waves of 64 x 32
+#define S2FIR_LAUNCH(NCW, WN) launch_s2fir<NCW, WN, 1, MOD>(y, xb_out, x, wplanes, bias, resid, p, f, stream, in_scale, out_scale)
+    if (p->Cout > 128 && eight) return S2FIR_LAUNCH(8, 8);                     // N tile 256
+    if (p->Cout > 64) return eight ? S2FIR_LAUNCH(8, 4) : S2FIR_LAUNCH(4, 4);  // 128: 2 x 4 waves of 64 x 32 / 1 x 4 waves of 128 x 32
+    return eight ? S2FIR_LAUNCH(8, 2) : S2FIR_LAUNCH(4, 2);                    // 64:  4 x 2 waves of 32 x 32 / 2 x 2 waves of 64 x 32
+#undef S2FIR_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int ideas_b3_blur_conv_s2(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v,
+                                     const float* bias, const void* resid, const ideas_conv_params* p, int xh, int xw, int pad0,
+                                     void* stream_) {
+    return blur_conv_s2<false>(y, xb_out, x, wplanes, fir_h, fir_v, nullptr, nullptr, bias, resid, p, xh, xw, pad0, stream_);
+}
+
+// The modulated form (MOD): in_scale float[B][Cin] on the blurred values, out_scale float[B][Cout] in the epilogue, either may be NULL;
+// with both NULL the unmodulated instantiations run (bitwise ideas_b3_blur_conv_s2).
+extern "C" int ideas_b3_blur_conv_s2_mod(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v,
+                                         const float* in_scale, const float* out_scale, const float* bias, const void* resid,
+                                         const ideas_conv_params* p, int xh, int xw, int pad0, void* stream_) {
+    if (!in_scale && !out_scale)
+        return blur_conv_s2<false>(y, xb_out, x, wplanes, fir_h, fir_v, nullptr, nullptr, bias, resid, p, xh, xw, pad0, stream_);
+    return blur_conv_s2<true>(y, xb_out, x, wplanes, fir_h, fir_v, in_scale, out_scale, bias, resid, p, xh, xw, pad0, stream_);
 }
 
 // The same LDS-image kernel WITHOUT the FIR (MODE 1): a plain 3x3 / stride-2 / unpadded convolution, optionally modulated.  Taken by

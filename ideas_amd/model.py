@@ -180,8 +180,8 @@ class ModulatedConv2d(nn.Module):
     def __init__(self, in_channel, out_channel, kernel_size, style_dim, demodulate=True, upsample=False,
                  downsample=False, blur_kernel=(1, 3, 3, 1)):
         super().__init__()
-        if downsample:
-            raise NotImplementedError("IDEAS never builds a downsampling ModulatedConv2d (models.py:143-152)")
+        if upsample and downsample:
+            raise ValueError("ModulatedConv2d: upsample and downsample are exclusive")
         self.eps = 1e-8
         self.kernel_size = kernel_size
         self.in_channel = in_channel
@@ -192,6 +192,10 @@ class ModulatedConv2d(nn.Module):
             factor = 2
             p = (len(blur_kernel) - factor) - (kernel_size - 1)
             self.blur = Blur(blur_kernel, pad=((p + 1) // 2 + factor - 1, p // 2 + 1), upsample_factor=factor)
+        if downsample:
+            factor = 2
+            p = (len(blur_kernel) - factor) + (kernel_size - 1)
+            self.blur = Blur(blur_kernel, pad=((p + 1) // 2, p // 2))
         self.scale = 1 / math.sqrt(in_channel * kernel_size ** 2)
         self.padding = kernel_size // 2
         self.weight = nn.Parameter(modconv_weight_layout(torch.randn(1, out_channel, in_channel, kernel_size, kernel_size), upsample))
@@ -201,13 +205,13 @@ class ModulatedConv2d(nn.Module):
     def forward(self, input, style, act: Optional[FusedLeakyReLU] = None, post_gain: float = 1.0,
                 resid: Optional[torch.Tensor] = None):
         s = self._styles(style)
-        fir = self.blur.kernel if self.upsample else None
+        fir = self.blur.kernel if (self.upsample or self.downsample) else None
         if act is None:
             return modulated_conv2d(input, self.weight, s, demodulate=self.demodulate, upsample=self.upsample, fir=fir,
-                                    eps=self.eps)
+                                    eps=self.eps, downsample=self.downsample)
         return modulated_conv2d(input, self.weight, s, demodulate=self.demodulate, upsample=self.upsample, fir=fir,
                                 eps=self.eps, act_bias=act.bias, negative_slope=act.negative_slope,
-                                act_scale=act.scale * post_gain, resid=resid)
+                                act_scale=act.scale * post_gain, resid=resid, downsample=self.downsample)
 
     def _styles(self, style):
         """s = modulation(style), memoised per (modulation weights, texture-code tensor) for the duration of a training iteration:

@@ -51,6 +51,9 @@ _BIAS_SUM_HIP = _os.environ.get("IDEAS_BIAS_SUM_HIP", "1") != "0"      # 0: auto
 BLUR_CONV = _os.environ.get("IDEAS_BLUR_CONV", "1") != "0"
 BLUR_CONV_MIN_OW = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_OW", "16"))      # below: the 8 x 16 output patch of the kernel would idle
 BLUR_CONV_MIN_BLOCKS = int(_os.environ.get("IDEAS_BLUR_CONV_MIN_BLOCKS", "512"))   # down_pair_ok: below, the two-kernel chain wins
+# the threshold of the MODULATED launch (mod_blur_conv_ok: the downsampling ModulatedConv2d), whose two-kernel chain is the blur + the
+# scaled stride-2 conv; a variable of its own, by default the unmodulated value
+BLUR_CONV_MOD_MIN_BLOCKS = int(_os.environ.get("IDEAS_BLUR_CONV_MOD_MIN_BLOCKS", str(BLUR_CONV_MIN_BLOCKS)))
 
 
 def wino_weights(w_ohwi: torch.Tensor) -> torch.Tensor:
@@ -713,20 +716,30 @@ def _blur_conv_plan(x_shape, w: torch.Tensor, fir: torch.Tensor, pad2):
     return L, hb, wb
 
 
-def blur_conv_s2_ok(x: torch.Tensor, w: torch.Tensor, fir: torch.Tensor, pad2, want_xb: bool = False) -> bool:
+def _blur_conv_blocks(L: Launch) -> int:
+    """Workgroups of the fused launch: 8 x 16 output patches x N tiles of 256 / 128 / 64 channels (the choice of
+    csrc/conv_b3_s2fir.hip::blur_conv_s2)."""
+    nt = 256 if L.Cout > 128 else 128 if L.Cout > 64 else 64
+    return L.B * ((L.OH + 7) // 8) * ((L.OW + 15) // 16) * ((L.Cout + nt - 1) // nt)
+
+
+def blur_conv_s2_ok(x: torch.Tensor, w: torch.Tensor, fir: torch.Tensor, pad2, want_xb: bool = False, min_blocks: int = 0) -> bool:
     if x.dtype != torch.float32 or not x.is_cuda:
         return False
     pl = _blur_conv_plan(tuple(x.shape), w, fir, pad2)
     if pl is None or fir_factors(fir) is None:
         return False
     L, hb, wb = pl
-    return (not want_xb) or (hb == 2 * L.OH + 1 and wb == 2 * L.OW + 1)
+    if want_xb and not (hb == 2 * L.OH + 1 and wb == 2 * L.OW + 1):
+        return False
+    return _blur_conv_blocks(L) >= min_blocks
 
 
 def blur_conv_s2_raw(x, w, fir, pad2, gain: float, bias=None, act: bool = False, act_gain: float = 1.0, alpha: float = 0.2,
-                     resid=None, want_xb: bool = False):
+                     resid=None, want_xb: bool = False, lin=None, lout=None):
     """``epilogue(gain * conv2d(upfirdn2d(x, fir, pad=pad2), w, stride=2))`` in one launch -> (y, blurred tensor or None).
-    The caller has checked ``blur_conv_s2_ok``."""
+    The caller has checked ``blur_conv_s2_ok``.  ``lin`` [B, Cin] / ``lout`` [B, Cout] (f32, contiguous): the per-sample scales of a
+    modulated conv, on the blurred values / in the epilogue (ideas_b3_blur_conv_s2_mod); the blurred tensor returned is unscaled."""
     x = _nhwc(x)
     L, hb, wb = _blur_conv_plan(tuple(x.shape), w, fir, pad2)
     kh, kv = fir_factors(fir)
@@ -735,11 +748,25 @@ def blur_conv_s2_raw(x, w, fir, pad2, gain: float, bias=None, act: bool = False,
     xb = torch.empty((L.B, L.Cin, hb, wb), device=x.device, dtype=x.dtype, memory_format=CL) if want_xb else None
     if resid is not None:
         resid = _nhwc(resid)
+    if lin is not None or lout is not None:
+        rc = _lib.load().ideas_b3_blur_conv_s2_mod(_lib.ptr(y), _lib.ptr(xb), _lib.ptr(x), _lib.ptr(b3_planes(L)), kh, kv, _lib.ptr(lin),
+                                                   _lib.ptr(lout), _lib.ptr(None if bias is None else bias.contiguous()),
+                                                   _lib.ptr(resid), C.byref(p), x.shape[2], x.shape[3], int(pad2[0]), _lib.stream_ptr())
+        _lib.check(rc, "ideas_b3_blur_conv_s2_mod")
+        return y, xb
     rc = _lib.load().ideas_b3_blur_conv_s2(_lib.ptr(y), _lib.ptr(xb), _lib.ptr(x), _lib.ptr(b3_planes(L)), kh, kv,
                                            _lib.ptr(None if bias is None else bias.contiguous()), _lib.ptr(resid), C.byref(p),
                                            x.shape[2], x.shape[3], int(pad2[0]), _lib.stream_ptr())
     _lib.check(rc, "ideas_b3_blur_conv_s2")
     return y, xb
+
+
+def mod_blur_conv_ok(x: torch.Tensor, w: torch.Tensor, fir: torch.Tensor, pad2, want_xb: bool = False) -> bool:
+    """Where the downsampling modulated conv takes the fused launch (``blur_conv_s2_raw(lin=, lout=)``): what ``blur_conv_s2_ok``
+    covers -- f32 activations, the split-bf16 contraction, a separable 4x4 FIR, Cin % 16 == 0, >= 8 x 16 output pixels, with
+    ``want_xb`` the blurred size 2 OH + 1 -- and at least BLUR_CONV_MOD_MIN_BLOCKS workgroups, the rule of ``down_pair_ok`` with a
+    threshold of its own."""
+    return blur_conv_s2_ok(x, w, fir, pad2, want_xb, min_blocks=BLUR_CONV_MOD_MIN_BLOCKS)
 
 
 class _DownPair(Function):
@@ -798,9 +825,7 @@ def down_pair_ok(input: torch.Tensor, w1, w2, fir, pad2, padding1: int = 1) -> b
     # Fewer than two workgroups per CU: every block's producers repeat the blur for its N tile and nothing hides the tail, the
     # blur kernel + generic stride-2 conv is as fast or faster (profiles/r04_blur_conv_microbench.txt: E.4.conv2 0.29 against 0.25 ms,
     # Dreal.4.conv2 a tie)
-    L = pl[0]
-    nt = 256 if L.Cout > 128 else 128 if L.Cout > 64 else 64
-    return L.B * ((L.OH + 7) // 8) * ((L.OW + 15) // 16) * ((L.Cout + nt - 1) // nt) >= BLUR_CONV_MIN_BLOCKS
+    return _blur_conv_blocks(pl[0]) >= BLUR_CONV_MIN_BLOCKS
 
 
 def down_pair(input: torch.Tensor, w1, b1, w2, b2, fir, pad2, padding1: int = 1, reflect1: bool = False, gain1: float = 1.0,

@@ -1,7 +1,7 @@
 """Modulated / demodulated 3x3 convolution without per-sample weights.
 
-Mirror of ``ModulatedConv2d.forward`` (stylegan2/model.py:236-277; same-resolution and upsample branches —
-the only two IDEAS instantiates, models.py:143-152).  The reference materialises a [B*Cout, Cin, 3, 3] weight
+Mirror of ``ModulatedConv2d.forward`` (stylegan2/model.py:236-277; the same-resolution and upsample branches IDEAS
+instantiates, models.py:143-152, and the downsample branch of the layer library).  The reference materialises a [B*Cout, Cin, 3, 3] weight
 per call and runs a ``groups=batch`` conv (B small convs for cuDNN).  Here the arithmetic is re-associated:
 
     y[b,o] = (scale * d[b,o]) * sum_{i,k} W[o,i,k] * (s[b,i] * x[b,i, . + k])
@@ -24,11 +24,12 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..precision import to_act, to_f32
+from . import conv as _conv
 from .conv import conv2d, conv_dgrad_raw, conv_fwd_raw, conv_transpose2d, conv_wgrad_raw, _nhwc
 from .conv_plan import ConvGeom, convT_out_size
 from . import conv_plan
 from . import scratch
-from .upfirdn2d import blur_bias_act, upfirdn2d
+from .upfirdn2d import _geometry, blur_bias_act, upfirdn2d, upfirdn2d_raw
 from .fused_act import bias_sink, fused_leaky_relu
 from .grad_sink import weight_grad
 
@@ -240,6 +241,78 @@ class _ModConvAct(Function):
         return (gx if need_x else None), gw, (gs if need_s else None), (gb if need_b else None), None, None, None, None
 
 
+class _ModConvDown(Function):
+    """The downsample branch (stylegan2/model.py:210-216, 263-269): Blur, then the stride-2 modulated conv, re-associated like the
+    other branches -- the blur is linear and per channel, so the style scales the BLURRED activation:
+
+        y[b,o] = gain * d[b,o] * sum_{i,k} W[o,i,k] * (s[b,i] * xb[b,i, 2. + k]),   xb = upfirdn2d(x, fir, pad2)
+
+    optionally with bias + leaky-ReLU in the conv epilogue (``b``).  Forward: ONE kernel (ideas_b3_blur_conv_s2_mod) where
+    ``mod_blur_conv_ok`` admits the shape, else the blur kernel + the scaled stride-2 conv (a 1x1 kernel: the decimating FIR + an
+    unstrided 1x1 conv, as ConvLayer's skip branch).  The blurred tensor is kept only for the weight gradient (the fused kernel's side
+    output); the style gradient's direct term is taken on the raw side, <x, B^T g> = <B x, g> per sample and channel."""
+
+    @staticmethod
+    def forward(ctx, x, w, s, b, fir, pad2, gain: float, demod: bool, eps: float, slope: float, act_gain: float):
+        x = _nhwc(x)
+        bias_param = b
+        s = s.contiguous()
+        act = b is not None
+        if act:
+            b = b.contiguous()
+        d = demod_of(w, s, gain, eps) if demod else None
+        k = w.shape[2]
+        need_w = ctx.needs_input_grad[1]
+        down = 2 if k == 1 else 1
+        pad4, bhw, g_pad = _geometry((x.shape[2], x.shape[3]), fir, 1, down, pad2)
+        g = ConvGeom(k, k, 1 if k == 1 else 2, 0, False)
+        if k == 3 and _conv.mod_blur_conv_ok(x, w, fir, pad2, want_xb=need_w):
+            y, xb = _conv.blur_conv_s2_raw(x, w, fir, pad2, gain, bias=b, act=act, act_gain=act_gain, alpha=slope, want_xb=need_w,
+                                           lin=s, lout=d)
+        else:
+            xb = upfirdn2d_raw(x, fir, (1, 1), (down, down), pad4, bhw, flip=True)
+            y = conv_fwd_raw(xb, w, g, gain, lin=s, lout=d, bias=b, act=act, act_gain=act_gain, alpha=slope)
+        ctx.g, ctx.gain, ctx.has_d, ctx.eps, ctx.act, ctx.slope, ctx.act_gain = g, gain, d is not None, eps, act, slope, act_gain
+        ctx.down, ctx.bhw, ctx.g_pad = down, bhw, g_pad
+        ctx.bias_ref = bias_param
+        none = s.new_zeros(0)
+        keep_y = act or d is not None         # read by the activation backward / the demodulation term only
+        ctx.save_for_backward(x, w, s, d if d is not None else none, y if keep_y else none, xb if need_w else none,
+                              b if act else none, fir)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, w, s, d, y, xb, b, fir = ctx.saved_tensors
+        d = d if ctx.has_d else None
+        g, gain = ctx.g, ctx.gain
+        need_x, need_w, need_s, need_b = ctx.needs_input_grad[:4]
+        gb = dot_d = None
+        if ctx.act:
+            gpre, gb, dot_d = act_bwd_dot(gy, y, b, ctx.slope, ctx.act_gain, bias_grad_into=bias_sink(ctx.bias_ref) if need_b else None)
+        else:
+            gpre = gy = _nhwc(gy)
+        gx = gw = gs = gq = None
+        if need_x or need_s:
+            gxb = conv_dgrad_raw(gpre, w, g, ctx.bhw, gain, lin=d, lout=s)
+            gx = upfirdn2d_raw(gxb, fir, (ctx.down, ctx.down), (1, 1), ctx.g_pad, (x.shape[2], x.shape[3]), flip=False)
+        if need_s or (need_w and d is not None):
+            dot_s = pixel_dot(x, gx) if need_s else scratch.zeros(tuple(s.shape), s.device, torch.float64)
+            if d is not None and dot_d is None:
+                dot_d = pixel_dot(gy, y)
+            gs, gq = _style_grads(dot_s, dot_d, s, d, w, gain, ctx.eps)
+        if need_w:
+            def grad(out):
+                r = conv_wgrad_raw(gpre, xb, g, tuple(w.shape), gain, lin=s, lout=d, out=out)
+                if gq is not None:
+                    _demod_wgrad(r, w, gq, s, gain)
+                return r
+            gw = weight_grad(w, grad, gpre, xb, s, d, gq)
+        return ((gx if need_x else None), gw, (gs if need_s else None), (gb if (ctx.act and need_b) else None),
+                None, None, None, None, None, None, None)
+
+
 _SECOND_ORDER = [False]
 
 
@@ -258,11 +331,19 @@ class second_order:
         _SECOND_ORDER[0] = self.prev
 
 
-def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale):
+def _down_pad(fir: torch.Tensor, k: int):
+    """The pads of the downsample branch's Blur (stylegan2/model.py:212-216)."""
+    p = (fir.shape[0] - 2) + (k - 1)
+    return (p + 1) // 2, p // 2
+
+
+def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale, downsample=False):
     cout, cin, k, _ = w.shape
     scale = 1.0 / math.sqrt(cin * k * k)
     xs = x * style.view(style.shape[0], cin, 1, 1)
-    if upsample:
+    if downsample:
+        y = conv2d(upfirdn2d(xs, fir, pad=_down_pad(fir, k)), w, None, stride=2, padding=0, gain=scale)
+    elif upsample:
         y = conv_transpose2d(xs, w.transpose(0, 1), None, stride=2, gain=scale)
     else:
         y = conv2d(xs, w, None, stride=1, padding=k // 2, gain=scale)
@@ -281,20 +362,34 @@ def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act
 def modulated_conv2d(x: torch.Tensor, weight: torch.Tensor, style: torch.Tensor, demodulate: bool = True,
                      upsample: bool = False, fir: Optional[torch.Tensor] = None, eps: float = 1e-8,
                      act_bias: Optional[torch.Tensor] = None, negative_slope: float = 0.2,
-                     act_scale: float = 2 ** 0.5, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     act_scale: float = 2 ** 0.5, resid: Optional[torch.Tensor] = None, downsample: bool = False) -> torch.Tensor:
     """``x`` [B,Cin,H,W]; ``weight`` [1,Cout,Cin,k,k] (the reference's parameter); ``style`` [B,Cin] = the
     already-affine-transformed modulation (stylegan2/model.py:239).  ``fir`` = the 4x4 blur (
     here) used after the stride-2 transposed conv (stylegan2/model.py:202-208, 258-261); it already carries the x4
-    upsample gain.  ``act_bias`` fuses the FusedLeakyReLU that always follows (stylegan2/model.py:374-375)."""
+    upsample gain.  ``act_bias`` fuses the FusedLeakyReLU that always follows (stylegan2/model.py:374-375).
+    ``downsample``: the Blur (``fir``, unit gain, pads of stylegan2/model.py:212-216) in front of a stride-2 conv (:263-269)."""
+    if upsample and downsample:
+        raise ValueError("modulated_conv2d: upsample and downsample are exclusive")
     _lib.require_cuda(x, weight, style)
+    if downsample:
+        if fir is None:
+            raise RuntimeError("modulated_conv2d(downsample=True) needs the blur FIR")
+        if resid is not None:
+            raise RuntimeError("modulated_conv2d(resid=...) is the no-grad fast path of the fused same-resolution conv")
+        _lib.require_cuda(fir, act_bias)
     x, style = to_act(x), to_f32(style)
     if resid is not None:
         resid = to_act(resid)
     w = weight[0] if weight.dim() == 5 else weight
     cout, cin, k, _ = w.shape
     if _SECOND_ORDER[0] and torch.is_grad_enabled() and resid is None:
-        return _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale)
+        return _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale, downsample)
     scale = 1.0 / math.sqrt(cin * k * k)
+    if downsample:
+        fuse = act_bias is not None and demodulate and cout % 4 == 0
+        y = _ModConvDown.apply(x, w, style, act_bias if fuse else None, fir, _down_pad(fir, k), scale, bool(demodulate), float(eps),
+                               float(negative_slope), float(act_scale))
+        return y if (fuse or act_bias is None) else fused_leaky_relu(y, act_bias, negative_slope, act_scale)
     fuse_act = act_bias is not None and not upsample and demodulate and cout % 4 == 0
     if resid is not None:
         if not fuse_act or torch.is_grad_enabled():

@@ -316,6 +316,20 @@ int ideas_conv_igemm_multi(int n, void* y, const void* x, const void* const* wma
 int ideas_b3_blur_conv_s2_supported(const ideas_conv_params* p, int xh, int xw, int pad0);
 int ideas_b3_blur_conv_s2(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v,
                           const float* bias, const void* resid, const ideas_conv_params* p, int xh, int xw, int pad0, void* stream);
+/* The same kernel for the downsampling ModulatedConv2d (stylegan2/model.py:210-216 Blur, :263-269 F.conv2d(stride=2, groups=batch)) in
+ * the re-associated form of ideas_conv_igemm's per-sample scales -- the blur is linear and per channel, so
+ *     y[b,o] = epilogue( gain * out_scale[b,o] * sum_{i,k} W[o,i,k] * (in_scale[b,i] * xb[b,i, 2. + k]) ),  xb = the blurred tensor:
+ *   in_scale  float[B][Cin] (16-byte aligned), multiplied into the blurred f32 value with ONE rounding before the 3-way split -- the
+ *             staged operand is bitwise in_scale * (the stand-alone blur's output), what ideas_conv_igemm(in_scale) stages behind a
+ *             blur pass;
+ *   out_scale float[B][Cout], multiplied into the accumulator after `gain` and before the bias, as ideas_conv_igemm does;
+ *   xb_out    stays the UNSCALED blurred tensor (ideas_conv_wgrad applies in_scale itself).
+ * Either scale may be NULL (= 1); with both NULL the result is bitwise that of ideas_b3_blur_conv_s2.  Every other argument, the
+ * argument checks and ideas_b3_blur_conv_s2_supported are those of ideas_b3_blur_conv_s2.
+ * (Additive within ABI 4: no signature changed; IDEAS_ABI_VERSION stays 4.) */
+int ideas_b3_blur_conv_s2_mod(void* y, void* xb_out, const void* x, const void* wplanes, const float* fir_h, const float* fir_v,
+                              const float* in_scale, const float* out_scale, const float* bias, const void* resid,
+                              const ideas_conv_params* p, int xh, int xw, int pad0, void* stream);
 
 /* Generic direct convolution (VALU) with the same parameterisation and epilogue; any Cin/Cout. Used for the
  * handful of tiny-K layers (RGB / N-channel inputs) where the MFMA tile would be empty. */

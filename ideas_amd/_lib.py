@@ -75,6 +75,7 @@ class LinearSeg(C.Structure):
 
 
 LINEAR_MAX_SEGMENTS = 32
+MBSTD_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_MBSTD_MAX_PARTIALS
 
 _P = C.c_void_p
 _PROTOS = {
@@ -134,6 +135,9 @@ _PROTOS = {
     "ideas_linear_bwd_x": (C.c_int, [C.POINTER(LinearSeg), C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "ideas_linear_bwd_w": (C.c_int, [C.POINTER(LinearSeg), C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ideas_act_bwd_dot": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
+    "ideas_mbstd_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
+    "ideas_mbstd_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
+    "ideas_mbstd_bwd2": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

@@ -2,7 +2,9 @@
 
 Host-side mirror of the subset of stylegan2/model.py that models.py imports (models.py:7):
 ``make_kernel`` (:22-30), ``Blur`` (:75-91), ``EqualConv2d`` (:94-123), ``EqualLinear`` (:132-161),
-``ScaledLeakyReLU`` (:169-178), ``ModulatedConv2d`` (:181-277), ``StyledConv_without_noise`` (:343-377).
+``ScaledLeakyReLU`` (:169-178), ``ModulatedConv2d`` (:181-277), ``StyledConv_without_noise`` (:343-377), and -- beyond what the
+IDEAS networks use -- the discriminator side ``ConvLayer`` (:584-630), ``ResBlock`` (:633-651), ``Discriminator`` (:654-712), which live
+in stylegan2_disc.py and are re-exported here on first access (they build on models.py, which imports this module).
 Same constructor signatures, parameter names, shapes and *creation order* (so ``torch.manual_seed(s)``
 reproduces the reference's initial weights and state-dicts interchange), but every forward runs on the
 gfx950 kernels: activations NHWC, conv weights kept OHWI in memory, the equalised-lr scale folded into the
@@ -22,6 +24,14 @@ from .op.linear import equal_linear
 from .op import FusedLeakyReLU, conv2d, conv2d_bias_act, fused_leaky_relu, modulated_conv2d, upfirdn2d
 
 CL = torch.channels_last
+_DISC_NAMES = ("ConvLayer", "ResBlock", "Discriminator")
+
+
+def __getattr__(name):
+    if name in _DISC_NAMES:
+        from . import stylegan2_disc
+        return getattr(stylegan2_disc, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def make_kernel(k: Sequence[float]) -> torch.Tensor:

@@ -381,6 +381,31 @@ int ideas_pixel_dot(double* out, const void* a, const void* g, int B, int64_t P,
 int ideas_act_bwd_dot(void* gpre, float* bias_grad, double* dot, const void* gy, const void* out, const float* bias,
                       const float* gpre_scale, int B, int64_t P, int C, float alpha, float act_gain, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Minibatch standard deviation of the StyleGAN2 discriminator (stylegan2/model.py:697-705), csrc/minibatch_stddev.hip.
+ * x [B,H,W,C] channels-innermost, f32 or bf16 (statistics in f32, chunk sums in double).  G = min(B, group) (<= 16: the group is
+ * held in registers), M = B / G, sample n = g*M + m (the group index is the OUTER one), K = (C / feat) * H * W:
+ *     mu[m,c,p] = mean_g x[g*M+m,c,p];   u = x - mu;   sd[m,c,p] = sqrt(mean_g u^2 + eps)        (biased, centred first)
+ *     s[m,f]    = (1/K) sum_{c in chunk f, p} sd[m,c,p]
+ *   ideas_mbstd_fwd   out [B,H,W,C+feat]: out[n,:C] = x[n] (exact), out[n,C+f,p] = s[n % M, f].
+ *   ideas_mbstd_bwd   gx [B,H,W,C] = gout[:,:C] + a u / sd with a[m,f] = (sum_{g,p} gout[g*M+m,C+f,p]) / (K G); a_out float[M*feat]
+ *                     receives a (the operand of ideas_mbstd_bwd2).
+ *   ideas_mbstd_bwd2  the backward of ideas_mbstd_bwd for the cotangent v = ggx [B,H,W,C]:
+ *                     dgout [B,H,W,C+feat]: dgout[:,:C] = v, dgout[n,C+f,p] = (1/(K G)) sum_{g, c in chunk f, p} v u / sd;
+ *                     dx [B,H,W,C] = a ((v - mean_g v) / sd - u (sum_g v u) / (G sd^3)).
+ * workspace (fwd, bwd2): M * feat * IDEAS_MBSTD_MAX_PARTIALS doubles, overwritten (one partial per block; a second small kernel adds
+ * them in index order).  No floating-point atomics: the results are bitwise reproducible.  A pixel of out / gout / dgout is C + feat
+ * elements, so those tensors are accessed element-wise (no 16-byte alignment is assumed or needed).
+ * IDEAS_E_SHAPE: B % G != 0 or C % feat != 0 (the reference's view() raises there too).
+ * (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#define IDEAS_MBSTD_MAX_PARTIALS 64
+int ideas_mbstd_fwd(void* out, void* workspace, const void* x, int B, int C, int H, int W, int group, int feat, float eps, int dtype,
+                    void* stream);
+int ideas_mbstd_bwd(void* gx, float* a_out, const void* gout, const void* x, int B, int C, int H, int W, int group, int feat, float eps,
+                    int dtype, void* stream);
+int ideas_mbstd_bwd2(void* dgout, void* dx, void* workspace, const void* ggx, const void* x, const float* a_in, int B, int C, int H,
+                     int W, int group, int feat, float eps, int dtype, void* stream);
+
 /* Adjoint of ReflectionPad2d(pad) in NHWC: gx [B,H,W,C] = fold of gpadded [B,H+2pad,W+2pad,C] (mirrored border rows /
  * columns added back onto their sources).  Any C (16-byte vectors when C % 4 == 0).  Used by the input gradient of the reflect-padded 3x3 convs of
  * E / Gstru / Ex (models.py:102-106). */

@@ -76,6 +76,7 @@ class LinearSeg(C.Structure):
 
 LINEAR_MAX_SEGMENTS = 32
 MBSTD_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_MBSTD_MAX_PARTIALS
+NOISE_ACT_MAX_PARTIALS = 2048     # include/ideas_hip.h::IDEAS_NOISE_ACT_MAX_PARTIALS
 
 _P = C.c_void_p
 _PROTOS = {
@@ -138,6 +139,8 @@ _PROTOS = {
     "ideas_mbstd_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
     "ideas_mbstd_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
     "ideas_mbstd_bwd2": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
+    "ideas_noise_bias_act": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, _P]),
+    "ideas_noise_bias_act_bwd": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

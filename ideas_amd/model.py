@@ -4,7 +4,9 @@ Host-side mirror of the subset of stylegan2/model.py that models.py imports (mod
 ``make_kernel`` (:22-30), ``Blur`` (:75-91), ``EqualConv2d`` (:94-123), ``EqualLinear`` (:132-161),
 ``ScaledLeakyReLU`` (:169-178), ``ModulatedConv2d`` (:181-277), ``StyledConv_without_noise`` (:343-377), and -- beyond what the
 IDEAS networks use -- the discriminator side ``ConvLayer`` (:584-630), ``ResBlock`` (:633-651), ``Discriminator`` (:654-712), which live
-in stylegan2_disc.py and are re-exported here on first access (they build on models.py, which imports this module).
+in stylegan2_disc.py and are re-exported here on first access (they build on models.py, which imports this module), and the generator side
+``PixelNorm`` (:14-19), ``Upsample`` / ``Downsample`` (:33-72), ``NoiseInjection`` (:280-291), ``ConstantInput`` (:294-304), ``StyledConv``
+(:307-341), ``ToRGB`` (:380-399), ``Generator`` (:402-581) in stylegan2_gen.py, re-exported the same way.
 Same constructor signatures, parameter names, shapes and *creation order* (so ``torch.manual_seed(s)``
 reproduces the reference's initial weights and state-dicts interchange), but every forward runs on the
 gfx950 kernels: activations NHWC, conv weights kept OHWI in memory, the equalised-lr scale folded into the
@@ -25,12 +27,16 @@ from .op import FusedLeakyReLU, conv2d, conv2d_bias_act, fused_leaky_relu, modul
 
 CL = torch.channels_last
 _DISC_NAMES = ("ConvLayer", "ResBlock", "Discriminator")
+_GEN_NAMES = ("PixelNorm", "Upsample", "Downsample", "NoiseInjection", "ConstantInput", "StyledConv", "ToRGB", "Generator")
 
 
 def __getattr__(name):
     if name in _DISC_NAMES:
         from . import stylegan2_disc
         return getattr(stylegan2_disc, name)
+    if name in _GEN_NAMES:
+        from . import stylegan2_gen
+        return getattr(stylegan2_gen, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -1,13 +1,14 @@
 """Custom ops of the IDEAS hot path on hand-written gfx950 kernels (C ABI: include/ideas_hip.h).
 
-Same public names as the reference's ``stylegan2.op`` (stylegan2/op/__init__.py:1-2) plus the conv family and the
-discriminator's minibatch standard deviation.
+Same public names as the reference's ``stylegan2.op`` (stylegan2/op/__init__.py:1-2) plus the conv family, the
+discriminator's minibatch standard deviation and the generator's fused noise injection + bias + activation.
 """
 from .fused_act import FusedLeakyReLU, fused_leaky_relu
 from .upfirdn2d import upfirdn2d
 from .conv import conv2d, conv2d_bias_act, conv_transpose2d
 from .modulated_conv import modulated_conv2d
 from .minibatch_stddev import minibatch_stddev
+from .noise_act import noise_bias_act
 
 __all__ = ["FusedLeakyReLU", "fused_leaky_relu", "upfirdn2d", "conv2d", "conv2d_bias_act", "conv_transpose2d", "modulated_conv2d",
-           "minibatch_stddev"]
+           "minibatch_stddev", "noise_bias_act"]

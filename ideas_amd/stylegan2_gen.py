@@ -1,0 +1,228 @@
+"""The generator side of the layer library: ``PixelNorm``, ``Upsample``, ``Downsample``, ``NoiseInjection``, ``ConstantInput``,
+``StyledConv`` (the noise-injecting one), ``ToRGB`` and ``Generator`` of stylegan2/model.py:14-72, 280-341, 380-581.
+
+Same constructor signatures, attribute names and parameter / buffer creation order as the reference, so state-dict keys and shapes
+match a reference generator checkpoint and ``torch.manual_seed(s)`` yields the reference's initial weights.  Importable from
+``ideas_amd.model`` (re-exported lazily, as the discriminator side is).
+
+The forwards run on the project's ops: ``ModulatedConv2d`` (3x3 same-resolution, 3x3 upsampling with its blur, 1x1 without
+demodulation), one ``op.noise_bias_act`` pass for noise injection + bias + leaky-ReLU behind every ``StyledConv``, ``upfirdn2d`` for
+``Upsample`` / ``Downsample`` and ``upfirdn2d_up2_add`` for "upsample the skip and add" in ``ToRGB``.  ``PixelNorm`` and
+``ConstantInput`` act on ``[B, style_dim]`` and a 4x4 constant and are plain torch.
+"""
+from __future__ import annotations
+
+import math
+import random
+
+import torch
+from torch import nn
+
+from .model import EqualLinear, ModulatedConv2d, make_kernel, styles_for
+from .op import FusedLeakyReLU, noise_bias_act, upfirdn2d
+from .op.conv import _AddBias
+from .op.upfirdn2d import upfirdn2d_up2_add
+from .precision import to_f32
+
+
+class PixelNorm(nn.Module):
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, input):
+        return input * torch.rsqrt(torch.mean(input ** 2, dim=1, keepdim=True) + 1e-8)
+
+
+class Upsample(nn.Module):
+    """Zero-stuff by ``factor`` and FIR with ``factor**2`` gain (stylegan2/model.py:33-51)."""
+
+    def __init__(self, kernel, factor=2):
+        super().__init__()
+        self.factor = factor
+        kernel = make_kernel(kernel) * (factor ** 2)
+        self.register_buffer("kernel", kernel)
+        p = kernel.shape[0] - factor
+        self.pad = ((p + 1) // 2 + factor - 1, p // 2)
+
+    def forward(self, input):
+        return upfirdn2d(input, self.kernel, up=self.factor, down=1, pad=self.pad)
+
+
+class Downsample(nn.Module):
+    """FIR and decimate by ``factor`` (stylegan2/model.py:54-72)."""
+
+    def __init__(self, kernel, factor=2):
+        super().__init__()
+        self.factor = factor
+        kernel = make_kernel(kernel)
+        self.register_buffer("kernel", kernel)
+        p = kernel.shape[0] - factor
+        self.pad = ((p + 1) // 2, p // 2)
+
+    def forward(self, input):
+        return upfirdn2d(input, self.kernel, up=1, down=self.factor, pad=self.pad)
+
+
+def _draw_noise(image):
+    b, _, h, w = image.shape
+    return torch.empty(b, 1, h, w, device=image.device, dtype=torch.float32).normal_()
+
+
+class NoiseInjection(nn.Module):
+    """``image + weight * noise`` (stylegan2/model.py:280-291).  Inside a ``StyledConv`` the module only holds ``weight``: the
+    injection runs fused with the bias and the activation (``op.noise_bias_act``)."""
+
+    def __init__(self):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(1))
+
+    def forward(self, image, noise=None):
+        if noise is None:
+            noise = _draw_noise(image)
+        return image + self.weight * noise
+
+
+class ConstantInput(nn.Module):
+    def __init__(self, channel, size=4):
+        super().__init__()
+        self.input = nn.Parameter(torch.randn(1, channel, size, size))
+
+    def forward(self, input):
+        return self.input.expand(input.shape[0], -1, -1, -1)      # (the reference repeats; the first conv reads it either way)
+
+
+class StyledConv(nn.Module):
+    """ModulatedConv2d -> NoiseInjection -> FusedLeakyReLU (stylegan2/model.py:307-341): the modulated conv (with its blur when
+    upsampling) without activation, then ONE pass for noise + bias + leaky-ReLU."""
+
+    def __init__(self, in_channel, out_channel, kernel_size, style_dim, upsample=False, blur_kernel=[1, 3, 3, 1], demodulate=True):
+        super().__init__()
+        self.conv = ModulatedConv2d(in_channel, out_channel, kernel_size, style_dim, upsample=upsample, blur_kernel=blur_kernel,
+                                    demodulate=demodulate)
+        self.noise = NoiseInjection()
+        self.activate = FusedLeakyReLU(out_channel)
+
+    def forward(self, input, style, noise=None):
+        out = self.conv(input, style)
+        if noise is None:
+            noise = _draw_noise(out)
+        return noise_bias_act(out, noise, self.noise.weight, self.activate.bias, self.activate.negative_slope, self.activate.scale)
+
+
+class ToRGB(nn.Module):
+    """1x1 modulated conv without demodulation + bias, added to the upsampled skip (stylegan2/model.py:380-399)."""
+
+    def __init__(self, in_channel, style_dim, upsample=True, blur_kernel=[1, 3, 3, 1]):
+        super().__init__()
+        if upsample:
+            self.upsample = Upsample(blur_kernel)
+        self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
+        self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
+
+    def forward(self, input, style, skip=None):
+        out = _AddBias.apply(self.conv(input, style), self.bias.view(-1))      # bias gradient on ideas_channel_sum
+        if skip is not None:
+            out = upfirdn2d_up2_add(skip, self.upsample.kernel, self.upsample.pad, out)
+        return out
+
+
+class Generator(nn.Module):
+    """z -> image (stylegan2/model.py:402-581); the image is f32 in every activation mode."""
+
+    def __init__(self, size, style_dim, n_mlp, channel_multiplier=2, blur_kernel=[1, 3, 3, 1], lr_mlp=0.01):
+        super().__init__()
+        self.size = size
+        self.style_dim = style_dim
+        layers = [PixelNorm()]
+        for _ in range(n_mlp):
+            layers.append(EqualLinear(style_dim, style_dim, lr_mul=lr_mlp, activation="fused_lrelu"))
+        self.style = nn.Sequential(*layers)
+        cm = channel_multiplier
+        self.channels = {4: 512, 8: 512, 16: 512, 32: 512, 64: 256 * cm, 128: 128 * cm, 256: 64 * cm, 512: 32 * cm, 1024: 16 * cm}
+        self.input = ConstantInput(self.channels[4])
+        self.conv1 = StyledConv(self.channels[4], self.channels[4], 3, style_dim, blur_kernel=blur_kernel)
+        self.to_rgb1 = ToRGB(self.channels[4], style_dim, upsample=False)
+        self.log_size = int(math.log(size, 2))
+        self.num_layers = (self.log_size - 2) * 2 + 1
+        self.convs = nn.ModuleList()
+        self.upsamples = nn.ModuleList()
+        self.to_rgbs = nn.ModuleList()
+        self.noises = nn.Module()
+        in_channel = self.channels[4]
+        for layer_idx in range(self.num_layers):          # (drawn before the convs, as the reference does)
+            res = (layer_idx + 5) // 2
+            self.noises.register_buffer(f"noise_{layer_idx}", torch.randn(1, 1, 2 ** res, 2 ** res))
+        for i in range(3, self.log_size + 1):
+            out_channel = self.channels[2 ** i]
+            self.convs.append(StyledConv(in_channel, out_channel, 3, style_dim, upsample=True, blur_kernel=blur_kernel))
+            self.convs.append(StyledConv(out_channel, out_channel, 3, style_dim, blur_kernel=blur_kernel))
+            self.to_rgbs.append(ToRGB(out_channel, style_dim))
+            in_channel = out_channel
+        self.n_latent = self.log_size * 2 - 2
+
+    def make_noise(self):
+        device = self.input.input.device
+        noises = [torch.randn(1, 1, 2 ** 2, 2 ** 2, device=device)]
+        for i in range(3, self.log_size + 1):
+            for _ in range(2):
+                noises.append(torch.randn(1, 1, 2 ** i, 2 ** i, device=device))
+        return noises
+
+    def mean_latent(self, n_latent):
+        latent_in = torch.randn(n_latent, self.style_dim, device=self.input.input.device)
+        return self.style(latent_in).mean(0, keepdim=True)
+
+    def get_latent(self, input):
+        return self.style(input)
+
+    def _modconvs(self):
+        """The modulated convs in the order the synthesis network reads the latent: conv1, to_rgb1, then (conv, conv, to_rgb) per block."""
+        convs = [self.conv1.conv, self.to_rgb1.conv]
+        for c1, c2, rgb in zip(self.convs[::2], self.convs[1::2], self.to_rgbs):
+            convs += [c1.conv, c2.conv, rgb.conv]
+        return convs
+
+    def _synthesis(self, first, at, noise):
+        """``at(i)``: the latent of layer position i."""
+        out = self.input(first)
+        out = self.conv1(out, at(0), noise=noise[0])
+        skip = self.to_rgb1(out, at(1))
+        i = 1
+        for conv1, conv2, noise1, noise2, to_rgb in zip(self.convs[::2], self.convs[1::2], noise[1::2], noise[2::2], self.to_rgbs):
+            out = conv1(out, at(i), noise=noise1)
+            out = conv2(out, at(i + 1), noise=noise2)
+            skip = to_rgb(out, at(i + 2), skip)
+            i += 2
+        return skip
+
+    def forward(self, styles, return_latents=False, inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
+                noise=None, randomize_noise=True):
+        if not input_is_latent:
+            styles = [self.style(s) for s in styles]
+        if noise is None:
+            if randomize_noise:
+                noise = [None] * self.num_layers
+            else:
+                noise = [getattr(self.noises, f"noise_{i}") for i in range(self.num_layers)]
+        if truncation < 1:
+            styles = [truncation_latent + truncation * (style - truncation_latent) for style in styles]
+        shared = None                                      # the ONE [B, D] latent every layer reads, if there is such a thing
+        if len(styles) < 2:
+            inject_index = self.n_latent
+            if styles[0].ndim < 3:
+                shared = styles[0]
+                latent = shared.unsqueeze(1).expand(-1, inject_index, -1)
+            else:
+                latent = styles[0]
+        else:
+            if inject_index is None:
+                inject_index = random.randint(1, self.n_latent - 1)
+            latent = torch.cat([styles[0].unsqueeze(1).expand(-1, inject_index, -1),
+                                styles[1].unsqueeze(1).expand(-1, self.n_latent - inject_index, -1)], 1)
+        if shared is not None:
+            # all layers read the same latent: their modulations come from one batched launch (model.styles_for, keyed on the tensor)
+            with styles_for(self._modconvs(), shared):
+                image = self._synthesis(shared, lambda i: shared, noise)
+        else:
+            image = self._synthesis(latent, lambda i: latent[:, i], noise)
+        return to_f32(image), (latent if return_latents else None)

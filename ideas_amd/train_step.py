@@ -445,13 +445,14 @@ def _train_iteration(trainer, args, X: torch.Tensor, iter_idx: int, draws: Optio
 
 def g_path_regularize(fake_img: torch.Tensor, latents: torch.Tensor, mean_path_length, decay: float = 0.01,
                       noise: Optional[torch.Tensor] = None):
-    """Path-length penalty (stylegan2/train.py:85-98) with ``latents`` = the texture code T [B, C]."""
+    """Path-length penalty (stylegan2/train.py:85-98) with ``latents`` = the texture code T [B, C], or the [B, n_latent, D] latents
+    of the StyleGAN2 ``Generator`` (the reference's reduction: sum over the last axis, then mean over the latent axis)."""
     import math
     if noise is None:
         noise = torch.randn_like(fake_img)
     noise = noise / math.sqrt(fake_img.shape[2] * fake_img.shape[3])
     (grad,) = torch.autograd.grad(outputs=(fake_img * noise).sum(), inputs=latents, create_graph=True)
-    path_lengths = torch.sqrt(grad.pow(2).sum(1))
+    path_lengths = torch.sqrt(grad.pow(2).sum(2).mean(1)) if grad.dim() == 3 else torch.sqrt(grad.pow(2).sum(1))
     path_mean = mean_path_length + decay * (path_lengths.mean() - mean_path_length)
     path_penalty = (path_lengths - path_mean).pow(2).mean()
     return path_penalty, path_mean.detach(), path_lengths

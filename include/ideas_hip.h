@@ -406,6 +406,29 @@ int ideas_mbstd_bwd(void* gx, float* a_out, const void* gout, const void* x, int
 int ideas_mbstd_bwd2(void* dgout, void* dx, void* workspace, const void* ggx, const void* x, const float* a_in, int B, int C, int H,
                      int W, int group, int feat, float eps, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Noise injection + bias + leaky-ReLU of a StyledConv (stylegan2/model.py:280-291, 335-341) in one pass, csrc/noise_act.hip.
+ * x / out / gy / gx [B,H,W,C] channels-innermost, f32 or bf16 (f32 arithmetic); noise float [noise_batch,H,W] with noise_batch = B
+ * or 1 (broadcast over the batch); noise_weight: ONE float in device memory (read by the kernels, never by the host); bias float[C].
+ *   ideas_noise_bias_act      out = lrelu(x + noise_weight * noise + bias[c], slope) * scale
+ *   ideas_noise_bias_act_bwd  from gy and the saved POST-activation out (sign(out) == sign(pre), as ideas_act_bwd_dot):
+ *                             gpre = (out > 0 ? gy : gy * slope) * scale
+ *                             gx = gpre;   gbias[c] += sum_{b,p} gpre   (float[C], ADDED to: the caller zeroes it; NULL: skipped)
+ *                             gnw[0] = sum_{b,p,c} gpre * noise         (overwritten)
+ *                             gnoise[bn,p] = noise_weight * sum_c gpre  (float [noise_batch,H,W], overwritten; summed over b when
+ *                                                                        noise_batch = 1; NULL: skipped)
+ * 16-byte vectors along C when C % 4 == 0 (% 8 for bf16) and every pointer is 16-byte aligned, an element-wise path for any other C.
+ * workspace (bwd): IDEAS_NOISE_ACT_MAX_PARTIALS doubles, followed by B*H*W floats when gnoise is given with noise_batch = 1 < B;
+ * overwritten.  gnw is summed without floating-point atomics (one double per block, added in a fixed order by a second small
+ * kernel): out, gx, gnw and gnoise are bitwise reproducible.  C <= 8192.
+ * IDEAS_E_SHAPE: a non-positive size or a noise_batch other than 1 or B.  (Additive within ABI 4.) */
+#define IDEAS_NOISE_ACT_MAX_PARTIALS 2048
+int ideas_noise_bias_act(void* out, const void* x, const float* noise, const float* noise_weight, const float* bias, int B, int C,
+                         int H, int W, int noise_batch, float slope, float scale, int dtype, void* stream);
+int ideas_noise_bias_act_bwd(void* gx, float* gbias, float* gnw, float* gnoise, void* workspace, const void* gy, const void* out,
+                             const float* noise, const float* noise_weight, int B, int C, int H, int W, int noise_batch, float slope,
+                             float scale, int dtype, void* stream);
+
 /* Adjoint of ReflectionPad2d(pad) in NHWC: gx [B,H,W,C] = fold of gpadded [B,H+2pad,W+2pad,C] (mirrored border rows /
  * columns added back onto their sources).  Any C (16-byte vectors when C % 4 == 0).  Used by the input gradient of the reflect-padded 3x3 convs of
  * E / Gstru / Ex (models.py:102-106). */

@@ -141,6 +141,9 @@ _PROTOS = {
     "ideas_mbstd_bwd2": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
     "ideas_noise_bias_act": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, _P]),
     "ideas_noise_bias_act_bwd": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, _P]),
+    "ideas_affine_warp": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "ideas_affine_warp_bwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 9 + [_P]),
+    "ideas_color_affine": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

@@ -1,7 +1,8 @@
 """Custom ops of the IDEAS hot path on hand-written gfx950 kernels (C ABI: include/ideas_hip.h).
 
 Same public names as the reference's ``stylegan2.op`` (stylegan2/op/__init__.py:1-2) plus the conv family, the
-discriminator's minibatch standard deviation and the generator's fused noise injection + bias + activation.
+discriminator's minibatch standard deviation, the generator's fused noise injection + bias + activation and the two image
+transforms of adaptive discriminator augmentation.
 """
 from .fused_act import FusedLeakyReLU, fused_leaky_relu
 from .upfirdn2d import upfirdn2d
@@ -9,6 +10,7 @@ from .conv import conv2d, conv2d_bias_act, conv_transpose2d
 from .modulated_conv import modulated_conv2d
 from .minibatch_stddev import minibatch_stddev
 from .noise_act import noise_bias_act
+from .augment import affine_warp, color_affine
 
 __all__ = ["FusedLeakyReLU", "fused_leaky_relu", "upfirdn2d", "conv2d", "conv2d_bias_act", "conv_transpose2d", "modulated_conv2d",
-           "minibatch_stddev", "noise_bias_act"]
+           "minibatch_stddev", "noise_bias_act", "affine_warp", "color_affine"]

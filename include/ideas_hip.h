@@ -463,6 +463,29 @@ int ideas_patch_resize_bwd(float* gx, const void* gy, const int* boxes, int n_cr
                            int out_w, int clear, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The image transforms of adaptive discriminator augmentation (stylegan2/non_leaking.py:316-391), csrc/augment.hip.
+ * x / y / gy in `layout` (IDEAS_NCHW or IDEAS_NHWC), f32 or bf16 with f32 arithmetic and one rounding at the store; any C >= 1.
+ *   ideas_affine_warp      theta: device float[B][6].  The source position, in pixels of x [B,C,H,W], of output pixel (ox, oy) is
+ *                              sx = t0*ox + t1*oy + t2,   sy = t3*ox + t4*oy + t5
+ *                          and y[b,c,oy,ox] ([B,C,OH,OW]) is the bilinear blend of the four pixels around (sx, sy); a tap outside
+ *                          [0,W-1] x [0,H-1] contributes zero (F.grid_sample(mode="bilinear", padding_mode="zeros"); the host folds
+ *                          align_corners=False and the grid's normalisation into theta).  A row of theta that is not finite gives
+ *                          zeros for that sample; the tap indices are clamped into the image before any address is formed.
+ *   ideas_affine_warp_bwd  the adjoint with respect to x: gx (ALWAYS f32, x's shape and `layout`) += sum over the same taps and
+ *                          weights of gy; `clear` != 0 zeroes gx first.  It scatters with f32 atomics, so the order of summation
+ *                          is not fixed (as in ideas_patch_resize_bwd and torch's own grid_sample backward).  No gradient for theta.
+ *   ideas_color_affine     C = 3.  m: device float[B][12], a row-major 3x4 per sample:
+ *                              y[b,i,p] = sum_j m[b][4i+j] * x[b,j,p] + m[b][4i+3]
+ *                          Its adjoint is the same call with the transposed 3x3 and a zero last column.
+ * NHWC with C % 4 == 0 (f32; C % 8 == 0 for bf16) and 16-byte aligned tensors moves 16-byte vectors along C.
+ * IDEAS_E_SHAPE: a non-positive size.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+int ideas_affine_warp(void* y, const void* x, const float* theta, int B, int C, int H, int W, int OH, int OW, int layout, int dtype,
+                      void* stream);
+int ideas_affine_warp_bwd(float* gx, const void* gy, const float* theta, int B, int C, int H, int W, int OH, int OW, int clear,
+                          int layout, int dtype, void* stream);
+int ideas_color_affine(void* y, const void* x, const float* m, int B, int H, int W, int layout, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

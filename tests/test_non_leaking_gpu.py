@@ -12,6 +12,7 @@ from test_bf16_gpu import close_bf16
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CL = torch.channels_last
+BF = torch.bfloat16
 TOL, GTOL = 1e-5, 1e-4            # forward / gradient, of the largest element
 
 
@@ -48,13 +49,24 @@ def thetas(rows, b=2):
 @pytest.mark.parametrize("layout", ("nchw", "nhwc"))
 @pytest.mark.parametrize("c", (1, 3, 4, 8))
 def test_affine_warp_exact_cases(op, c, layout):
+    _exact_cases(op, c, layout, torch.float32)
+
+
+@pytest.mark.parametrize("layout", ("nchw", "nhwc"))
+@pytest.mark.parametrize("c", (1, 3, 4, 8))
+def test_affine_warp_exact_cases_bf16(op, c, layout):
+    """NHWC: C = 4 (f32 would vectorise), 3 and 1 run the bf16 element kernel, C = 8 the 8-wide one."""
+    _exact_cases(op, c, layout, BF)
+
+
+def _exact_cases(op, c, layout, dtype):
     gen = torch.Generator().manual_seed(10 + c)
-    x = torch.randn(2, c, 9, 7, generator=gen)                      # H = 9, W = 7
+    x = torch.randn(2, c, 9, 7, generator=gen).to(dtype)            # H = 9, W = 7
     xd = fmt(x.to(DEV), layout)
     H, W = 9, 7
 
     y = op.affine_warp(xd, thetas([1, 0, 0, 0, 1, 0]), (H, W))
-    assert keeps_format(y, layout) and torch.equal(y.cpu(), x), "identity"
+    assert y.dtype == dtype and keeps_format(y, layout) and torch.equal(y.cpu(), x), "identity"
 
     # sx = ox + 2, sy = oy - 3: y[oy, ox] = x[oy - 3, ox + 2], zeros shifted in
     y = op.affine_warp(xd, thetas([1, 0, 2, 0, 1, -3]), (H, W))
@@ -69,10 +81,43 @@ def test_affine_warp_exact_cases(op, c, layout):
     y = op.affine_warp(xd, thetas([1, 0, W + 5, 0, 1, 0]), (H, W))
     assert torch.equal(y.cpu(), torch.zeros_like(x)), "every sample outside"
 
-    # sx = ox - 0.5: exactly half of each neighbour, a zero past the left edge
+    # sx = ox - 0.5: exactly half of each neighbour, a zero past the left edge; in f32 from the operands, one rounding at the store
     y = op.affine_warp(xd, thetas([1, 0, -0.5, 0, 1, 0]), (H, W))
-    left = torch.cat((torch.zeros(2, c, H, 1), x[..., :-1]), -1)
-    assert torch.equal(y.cpu(), 0.5 * (left + x)), "half-pixel shift"
+    left = torch.cat((torch.zeros(2, c, H, 1), x[..., :-1].float()), -1)
+    assert torch.equal(y.cpu(), (0.5 * (left + x.float())).to(dtype)), "half-pixel shift"
+
+
+@pytest.mark.parametrize("layout", ("nchw", "nhwc"))
+def test_affine_warp_boundary_positions_are_exact(op, layout):
+    """Positions on the two limits of (-1, W) x (-1, H) and a quarter-pixel shift of small integers, along x and along y."""
+    H, W = 9, 7
+    gen = torch.Generator().manual_seed(20)
+    x = torch.randn(2, 4, H, W, generator=gen)
+    xi = torch.randint(-8, 9, (2, 4, H, W), generator=gen).float()
+    warp = lambda t, row: op.affine_warp(fmt(t.to(DEV), layout), thetas(row), (H, W)).cpu()
+    zeros = torch.zeros_like(x)
+
+    want = zeros.clone()                                            # sx = ox - 1: the tap of ox = 0 at exactly -1 is outside
+    want[..., 1:] = x[..., :-1]
+    assert torch.equal(warp(x, [1, 0, -1, 0, 1, 0]), want), "x: tap at -1"
+    want = zeros.clone()                                            # sx = ox + W - 1: only ox = 0 is inside, at exactly W - 1
+    want[..., 0] = x[..., W - 1]
+    assert torch.equal(warp(x, [1, 0, W - 1, 0, 1, 0]), want), "x: tap at W - 1"
+    right = torch.cat((xi[..., 1:], torch.zeros(2, 4, H, 1)), -1)   # sx = ox + 0.25: 3/4 of x[ox], 1/4 of x[ox + 1] (zero past W - 1)
+    want = 0.75 * xi + 0.25 * right
+    assert torch.equal(want[..., W - 1], 0.75 * xi[..., W - 1])
+    assert torch.equal(warp(xi, [1, 0, 0.25, 0, 1, 0]), want), "x: quarter pixel"
+
+    want = zeros.clone()
+    want[:, :, 1:] = x[:, :, :-1]
+    assert torch.equal(warp(x, [1, 0, 0, 0, 1, -1]), want), "y: tap at -1"
+    want = zeros.clone()
+    want[:, :, 0] = x[:, :, H - 1]
+    assert torch.equal(warp(x, [1, 0, 0, 0, 1, H - 1]), want), "y: tap at H - 1"
+    below = torch.cat((xi[:, :, 1:], torch.zeros(2, 4, 1, W)), 2)
+    want = 0.75 * xi + 0.25 * below
+    assert torch.equal(want[:, :, H - 1], 0.75 * xi[:, :, H - 1])
+    assert torch.equal(warp(xi, [1, 0, 0, 0, 1, 0.25]), want), "y: quarter pixel"
 
 
 # ------------------------------------------------------------------------------------------------- general thetas
@@ -153,6 +198,124 @@ def test_affine_warp_general_bf16(op, case, layout):
     assert gx.dtype == torch.bfloat16
     close_bf16(y, y64, "y")
     close_bf16(gx, g64, "gx")
+
+
+# ------------------------------------------------------------------------------------------------- hostile thetas
+HOSTILE = {"nan coefficient": [1, float("nan"), 0, 0, 1, 0], "inf offset": [1, 0, float("inf"), 0, 1, 0],
+           "1e30 scale": [1e30, 0, 1e30, 0, 1e30, 1e30], "-1e30 offset": [1, 0, -1e30, 0, 1, 0]}
+
+
+@pytest.mark.parametrize("dtype", (torch.float32, BF), ids=("f32", "bf16"))
+@pytest.mark.parametrize("layout", ("nchw", "nhwc"))
+@pytest.mark.parametrize("c", (4, 8))
+def test_affine_warp_hostile_theta_zeroes_its_sample_only(op, c, layout, dtype):
+    """Sample 1 of three carries a theta that is not finite or whose positions overflow an int: its output and its input gradient
+    are exactly zero, and the neighbours are what they are beside an ordinary sample."""
+    H, W = 9, 7
+    gen = torch.Generator().manual_seed(30 + c)
+    x = torch.randn(3, c, H, W, generator=gen).to(dtype)
+    cot = torch.randn(3, c, H, W, generator=gen).to(dtype)
+    theta = general_theta(3, gen, (H, W), (H, W))
+    x64 = x[[0, 2]].double().requires_grad_(True)
+    y64 = grid_sample_f64(x64, theta[[0, 2]], (H, W))
+    (g64,) = torch.autograd.grad((y64 * cot[[0, 2]].double()).sum(), x64)
+    plain = op.affine_warp(fmt(x.to(DEV), layout), theta.to(DEV), (H, W))
+    for name, row in HOSTILE.items():
+        th = theta.clone()
+        th[1] = torch.tensor(row)
+        xd = fmt(x.to(DEV), layout).requires_grad_(True)
+        y = op.affine_warp(xd, th.to(DEV), (H, W))
+        (gx,) = torch.autograd.grad(y, xd, fmt(cot.to(DEV), layout))
+        assert float(y[1].abs().max()) == 0.0 and not bool(torch.isnan(y[1]).any()), name
+        assert torch.equal(y[[0, 2]], plain[[0, 2]]), name
+        assert float(gx[1].abs().max()) == 0.0 and not bool(torch.isnan(gx[1]).any()), name
+        if dtype == BF:
+            close_bf16(gx[[0, 2]], g64, name + " gx")
+        else:
+            e = rel_err(gx[[0, 2]], g64)
+            print(f"hostile theta ({name}) f32 {layout} C = {c}: gx of the neighbours {e:.2e}")
+            assert e <= GTOL, name
+
+
+# ------------------------------------------------------------------------------------------------- loaded atomics
+def _scale_theta(b, scale, offsets):
+    return torch.tensor([[scale, 0, offsets[i][0], 0, scale, offsets[i][1]] for i in range(b)], dtype=torch.float32)
+
+
+# (input shape, output size, theta): 96 x 96 outputs inside an 8 x 8 image -- about 144 land on each input pixel; 16 x 16 outputs
+# four pixels apart in a 64 x 64 image -- every tap is its input pixel's only contribution and three quarters get none
+ATOMIC = {"minify": ((2, 4, 8, 8), (96, 96), _scale_theta(2, 6.5 / 95, ((0.25, 0.25), (0.125, 0.375)))),
+          "magnify": ((2, 8, 64, 64), (16, 16), _scale_theta(2, 4.0, ((0.5, 0.25), (1.25, 2.75))))}
+_atomic_cache = {}
+
+
+def atomic_case(name, dtype):
+    """(x, theta, cot, reference output, reference input gradient) on operands rounded to ``dtype``, computed once."""
+    if (name, dtype) not in _atomic_cache:
+        shape, out_hw, theta = ATOMIC[name]
+        gen = torch.Generator().manual_seed(50 + len(name))
+        x = torch.randn(*shape, generator=gen).to(dtype)
+        cot = torch.randn(shape[0], shape[1], *out_hw, generator=gen).to(dtype)
+        x64 = x.double().requires_grad_(True)
+        y64 = grid_sample_f64(x64, theta, out_hw)
+        (g64,) = torch.autograd.grad((y64 * cot.double()).sum(), x64)
+        outside = float((y64.detach() == 0).double().mean())
+        assert outside == 0 if name == "minify" else outside < 0.9, outside
+        if name == "magnify":
+            assert float((g64 == 0).double().mean()) > 0.7
+        _atomic_cache[(name, dtype)] = (x, theta, cot, y64.detach(), g64)
+    return _atomic_cache[(name, dtype)]
+
+
+@pytest.mark.parametrize("dtype", (torch.float32, BF), ids=("f32", "bf16"))
+@pytest.mark.parametrize("layout", ("nchw", "nhwc"))
+@pytest.mark.parametrize("name", tuple(ATOMIC))
+def test_affine_warp_backward_under_atomic_load(op, name, layout, dtype):
+    x, theta, cot, y64, g64 = atomic_case(name, dtype)
+    out_hw = ATOMIC[name][1]
+    xd = fmt(x.to(DEV), layout).requires_grad_(True)
+    y = op.affine_warp(xd, theta.to(DEV), out_hw)
+    assert y.dtype == dtype and keeps_format(y, layout)
+    (gx,) = torch.autograd.grad(y, xd, fmt(cot.to(DEV), layout))
+    if dtype == BF:
+        close_bf16(y, y64, "y")
+        close_bf16(gx, g64, "gx")
+    else:
+        ey, eg = rel_err(y, y64), rel_err(gx, g64)
+        print(f"affine_warp {name} f32 {layout}: y {ey:.2e}  gx {eg:.2e}")
+        assert ey <= TOL and eg <= GTOL
+        lhs = float((y.detach().double() * cot.to(DEV).double()).sum())
+        rhs = float((xd.detach().double() * gx.double()).sum())
+        scale = float((y.detach().double() * cot.to(DEV).double()).abs().sum())
+        print(f"  adjoint: |{lhs:.6f} - {rhs:.6f}| = {abs(lhs - rhs):.2e}  vs 1e-5 * {scale:.3f}")
+        assert abs(lhs - rhs) <= 1e-5 * scale
+    if name == "magnify":
+        assert float(gx.cpu()[g64 == 0].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("layout", ("nchw", "nhwc"))
+def test_affine_warp_bwd_accumulates_without_clear(op, layout):
+    """ideas_affine_warp_bwd(clear = 0) adds to what gx holds; clear = 1 on the same buffer then gives the plain result, bitwise
+    where an input pixel has at most one contribution (everywhere in the magnification case)."""
+    from ideas_amd import _lib
+    x, theta, cot, _, g64 = atomic_case("magnify", torch.float32)
+    (b, c, h, w), (oh, ow) = ATOMIC["magnify"][0], ATOMIC["magnify"][1]
+    xd = fmt(x.to(DEV), layout).requires_grad_(True)
+    gy, th = fmt(cot.to(DEV), layout), theta.to(DEV)
+    (plain,) = torch.autograd.grad(op.affine_warp(xd, th, (oh, ow)), xd, gy)
+    prefill = fmt(torch.randn(b, c, h, w, generator=torch.Generator().manual_seed(51)).to(DEV), layout)
+    buf = prefill.clone(memory_format=torch.preserve_format)
+    assert keeps_format(buf, layout)
+    call = lambda clear: _lib.load().ideas_affine_warp_bwd(_lib.ptr(buf), _lib.ptr(gy), _lib.ptr(th), b, c, h, w, oh, ow, clear,
+                                                           _lib.NHWC if layout == "nhwc" else _lib.NCHW, _lib.F32, _lib.stream_ptr())
+    assert call(0) == 0
+    want = prefill.double() + plain.double()
+    e = float((buf.double() - want).abs().max()) / float(want.abs().max())
+    print(f"affine_warp_bwd clear = 0 {layout}: {e:.2e}")
+    assert e <= GTOL
+    assert torch.equal(buf[(g64 == 0).to(DEV)], prefill[(g64 == 0).to(DEV)])       # untouched where nothing lands
+    assert call(1) == 0
+    assert torch.equal(buf, plain)
 
 
 def test_affine_warp_fallback_dtypes_and_second_order(op):

@@ -18,6 +18,14 @@ TOL, GTOL = 1e-5, 1e-4
 
 OP_CASES = [(4, 8, 4, 4, 1), (8, 12, 4, 4, 1), (2, 8, 4, 4, 1), (3, 4, 2, 2, 1), (1, 8, 4, 4, 1), (8, 12, 3, 5, 2), (4, 5, 4, 4, 1),
             (8, 512, 4, 4, 1)]
+# (case, group) with more than four samples in a group: the kernels instantiated for up to 16 register-held samples, with G = 8,
+# an odd G (5), G = min(B, group) = 6 and the maximum 16
+GROUP_CASES = [((8, 12, 4, 4, 1), 8), ((16, 8, 3, 5, 2), 8), ((10, 6, 2, 2, 1), 5), ((6, 4, 2, 2, 1), 8), ((16, 8, 4, 4, 1), 16)]
+# K = 260 * 81 = 21060 columns: more than MBSTD_MAX_PARTIALS blocks of 256, so a block walks its column loop twice (the second
+# trip partial) and the fill kernel adds all the partials
+CAPPED_CASE = (4, 260, 9, 9, 1)
+_ids = lambda c: "x".join(map(str, c))
+_gids = lambda cg: _ids(cg[0]) + "-g%d" % cg[1]
 
 
 @pytest.fixture(scope="module")
@@ -25,21 +33,21 @@ def gold():
     return Golden("stylegan2_disc.npz")
 
 
-def _operands(case, dtype):
-    """x, gout, v as the kernels see them (rounded to ``dtype``), in f64 on the CPU."""
+def _operands(case, dtype, offset=0.0):
+    """x, gout, v as the kernels see them (rounded to ``dtype``), in f64 on the CPU; ``offset`` is added to x before the rounding."""
     b, c, h, w, feat = case
     g = torch.Generator().manual_seed(7 + sum(case))
-    rnd = lambda *s: torch.randn(*s, generator=g).to(dtype).double()
-    return rnd(b, c, h, w), rnd(b, c + feat, h, w), rnd(b, c, h, w)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    return (rnd(b, c, h, w) + offset).to(dtype).double(), rnd(b, c + feat, h, w).to(dtype).double(), rnd(b, c, h, w).to(dtype).double()
 
 
-def _run(case, x64, gout64, v64, dtype, fmt, second=True):
+def _run(case, x64, gout64, v64, dtype, fmt, second=True, group=4):
     """out, gx, (dgout, dx) of the op on the device."""
     import ideas_amd.op as op
     feat = case[4]
     x = x64.to(dtype).cuda().contiguous(memory_format=fmt).requires_grad_(True)
     gout = gout64.to(dtype).cuda().contiguous(memory_format=CL).requires_grad_(True)
-    out = op.minibatch_stddev(x, 4, feat)
+    out = op.minibatch_stddev(x, group, feat)
     (gx,) = torch.autograd.grad(out, x, gout, create_graph=True)
     if not second:
         return x, out, gx, None, None
@@ -47,48 +55,148 @@ def _run(case, x64, gout64, v64, dtype, fmt, second=True):
     return x, out, gx, dgout, dx
 
 
-@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
-@pytest.mark.parametrize("case", OP_CASES, ids=lambda c: "x".join(map(str, c)))
-def test_op_f32_vs_f64_restatement(case, fmt):
+def _trips(case):
+    """Passes of a block through its column loop: ceil(K / 256) blocks, at most MBSTD_MAX_PARTIALS, 256 columns a pass."""
+    from ideas_amd import _lib
     b, c, h, w, feat = case
-    x64, gout64, v64 = _operands(case, torch.float32)
-    x, out, gx, dgout, dx = _run(case, x64, gout64, v64, torch.float32, fmt)
+    k = (c // feat) * h * w
+    nblk = min(-(-k // 256), _lib.MBSTD_MAX_PARTIALS)
+    return -(-k // (nblk * 256))
+
+
+def _check_f32(case, fmt, group=4, ops=None):
+    b, c, h, w, feat = case
+    x64, gout64, v64 = ops if ops is not None else _operands(case, torch.float32)
+    x, out, gx, dgout, dx = _run(case, x64, gout64, v64, torch.float32, fmt, group=group)
     assert tuple(out.shape) == (b, c + feat, h, w) and out.dtype == torch.float32 and out.is_contiguous(memory_format=CL)
     assert torch.equal(out[:, :c], x.detach())                                   # the copy part is bit-exact
-    ref = R.minibatch_stddev(x64, 4, feat)
+    ref = R.minibatch_stddev(x64, group, feat)
     e = rel_err(out[:, c:], ref[:, c:])
-    print(case, "statistic", e)
+    print(case, group, "statistic", e)
     assert e < TOL, (case, e)
-    e = rel_err(gx, R.backward(x64, gout64, 4, feat))
-    print(case, "gx", e)
+    e = rel_err(gx, R.backward(x64, gout64, group, feat))
+    print(case, group, "gx", e)
     assert e < GTOL, (case, e)
-    ref_dgout, ref_dx = R.backward2(x64, gout64, v64, 4, feat)
+    ref_dgout, ref_dx = R.backward2(x64, gout64, v64, group, feat)
     assert torch.equal(dgout[:, :c], v64.float().cuda())
     e = rel_err(dgout[:, c:], ref_dgout[:, c:])
-    print(case, "d gout statistic channel", e)
+    print(case, group, "d gout statistic channel", e)
     assert e < GTOL, (case, e)
     if b > 1:
         e = rel_err(dx, ref_dx)
-        print(case, "d x", e)
+        print(case, group, "d x", e)
         assert e < GTOL, (case, e)
     else:
         assert float(dx.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("case", OP_CASES, ids=lambda c: "x".join(map(str, c)))
-def test_op_bf16_vs_f64_on_the_same_operands(case):
+def _check_bf16(case, group=4):
     """bf16 tensors, channels_last: statistics in f32, one rounding to bf16 at each store (the op bound of tests/test_bf16_gpu.py)."""
     b, c, h, w, feat = case
     x64, gout64, v64 = _operands(case, BF)
-    x, out, gx, dgout, dx = _run(case, x64, gout64, v64, BF, CL)
+    x, out, gx, dgout, dx = _run(case, x64, gout64, v64, BF, CL, group=group)
     assert out.dtype == BF and gx.dtype == BF and dx.dtype == BF
     assert torch.equal(out[:, :c], x.detach())
-    close_bf16(out[:, c:], R.minibatch_stddev(x64, 4, feat)[:, c:], "statistic")
-    close_bf16(gx, R.backward(x64, gout64, 4, feat), "gx")
-    ref_dgout, ref_dx = R.backward2(x64, gout64, v64, 4, feat)
+    close_bf16(out[:, c:], R.minibatch_stddev(x64, group, feat)[:, c:], "statistic")
+    close_bf16(gx, R.backward(x64, gout64, group, feat), "gx")
+    ref_dgout, ref_dx = R.backward2(x64, gout64, v64, group, feat)
     assert torch.equal(dgout[:, :c].double().cpu(), v64)
     close_bf16(dgout[:, c:], ref_dgout[:, c:], "d gout statistic channel")
     close_bf16(dx, ref_dx, "d x")
+
+
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
+def test_op_f32_vs_f64_restatement(case, fmt):
+    _check_f32(case, fmt)
+
+
+@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
+def test_op_bf16_vs_f64_on_the_same_operands(case):
+    _check_bf16(case)
+
+
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("cg", GROUP_CASES, ids=_gids)
+def test_op_f32_groups_above_four(cg, fmt):
+    """G in 5..16: all three orders against the restatement called with the same group."""
+    _check_f32(cg[0], fmt, group=cg[1])
+
+
+@pytest.mark.parametrize("cg", GROUP_CASES, ids=_gids)
+def test_op_bf16_groups_above_four(cg):
+    _check_bf16(cg[0], group=cg[1])
+
+
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+def test_op_f32_capped_grid_walks_the_column_loop_twice(fmt):
+    assert _trips(CAPPED_CASE) >= 2
+    _check_f32(CAPPED_CASE, fmt)
+
+
+def test_op_bf16_capped_grid_walks_the_column_loop_twice():
+    assert _trips(CAPPED_CASE) >= 2
+    _check_bf16(CAPPED_CASE)
+
+
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+def test_op_f32_large_mean_does_not_cancel(fmt):
+    """x = 100 + randn: var = E[x^2] - mean^2 in f32 loses 1e4 * 6e-8 of 1e4 against a variance of 1, and f32 centring comes back
+    multiplied by |x| sd / eps in the double backward (csrc/minibatch_stddev.hip::column_stats).  The usual bounds hold only for
+    two-pass statistics in double."""
+    case = (4, 8, 4, 4, 1)
+    ops = _operands(case, torch.float32, offset=100.0)
+    assert float(ops[0].mean()) > 99
+    _check_f32(case, fmt, ops=ops)
+
+
+@pytest.mark.parametrize("case,dtype", [((4, 8, 4, 4, 1), torch.float32), ((4, 8, 4, 4, 1), BF), ((3, 4, 2, 2, 1), torch.float32)],
+                         ids=["4x8x4x4x1-f32", "4x8x4x4x1-bf16", "3x4x2x2x1-f32"])
+def test_identical_samples_give_sqrt_eps_with_a_group(case, dtype):
+    """Zero variance with G > 1 (G = 3: sum / 3 is inexact): the statistic is sqrt(eps), u = 0 leaves gx = gout[:, :C], and the
+    double backward is a (v - mean_g v) / sd with sd = 1e-4: values in the hundreds."""
+    b, c, h, w, feat = case
+    x64, gout64, v64 = _operands(case, dtype)
+    x64 = x64[:1].expand(b, c, h, w).contiguous()
+    x, out, gx, dgout, dx = _run(case, x64, gout64, v64, dtype, CL)
+    assert torch.equal(out[:, :c], x.detach())
+    if dtype == BF:       # the f32 value rounded once at the store: 1e-4 is 209.7 steps of 2^-21, nowhere near a tie
+        assert torch.equal(out[:, c:].cpu(), torch.full((b, 1, h, w), 1e-4).to(BF))
+    else:
+        assert torch.allclose(out[:, c:].cpu(), torch.full((b, 1, h, w), 1e-4), rtol=1e-6, atol=0)
+    e = rel_err(gx, gout64[:, :c])
+    print(case, dtype, "gx vs gout[:, :C]", e)
+    assert e < GTOL, (case, e)
+    ref_dgout, ref_dx = R.backward2(x64, gout64, v64, 4, feat)
+    assert float(ref_dx.abs().max()) > 50
+    if dtype == BF:
+        close_bf16(dx, ref_dx, "d x")
+    else:
+        e = rel_err(dx, ref_dx)
+        print(case, dtype, "d x", e, "largest", float(ref_dx.abs().max()))
+        assert e < GTOL, (case, e)
+
+
+def test_group_of_seventeen_is_refused_and_writes_nothing():
+    """B = 17 with group 32 is G = 17, one more than the kernels hold in registers: the op raises, and each C entry point returns an
+    error without touching its outputs."""
+    import ideas_amd.op as op
+    from ideas_amd import _lib
+    b, c, h, w, feat, group = 17, 4, 2, 2, 1, 32
+    x = torch.randn(b, c, h, w, device="cuda").contiguous(memory_format=CL)
+    with pytest.raises(RuntimeError):
+        op.minibatch_stddev(x, group, feat)
+    lib, p, s = _lib.load(), _lib.ptr, _lib.stream_ptr()
+    sentinel = lambda *shape, dtype=torch.float32: torch.full(shape, -77.0, device="cuda", dtype=dtype)
+    out, gx, dgout, dx = sentinel(b, h, w, c + feat), sentinel(b, h, w, c), sentinel(b, h, w, c + feat), sentinel(b, h, w, c)
+    ws, a = sentinel(_lib.MBSTD_MAX_PARTIALS, dtype=torch.float64), sentinel(1)
+    gout, v = torch.randn(b, h, w, c + feat, device="cuda"), torch.randn(b, h, w, c, device="cuda")
+    assert lib.ideas_mbstd_fwd(p(out), p(ws), p(x), b, c, h, w, group, feat, 1e-8, _lib.F32, s) != 0
+    assert lib.ideas_mbstd_bwd(p(gx), p(a), p(gout), p(x), b, c, h, w, group, feat, 1e-8, _lib.F32, s) != 0
+    assert lib.ideas_mbstd_bwd2(p(dgout), p(dx), p(ws), p(v), p(x), p(a), b, c, h, w, group, feat, 1e-8, _lib.F32, s) != 0
+    torch.cuda.synchronize()
+    for t, name in ((out, "out"), (gx, "gx"), (dgout, "dgout"), (dx, "dx"), (ws, "workspace"), (a, "a")):
+        assert bool((t == -77.0).all()), name
 
 
 def test_single_sample_gives_sqrt_eps_and_no_extra_gradient():
@@ -102,12 +210,12 @@ def test_single_sample_gives_sqrt_eps_and_no_extra_gradient():
 
 @pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
 def test_two_runs_are_bitwise_equal(dtype):
-    case = (8, 512, 4, 4, 1)
-    ops = _operands(case, dtype)
-    a = _run(case, *ops, dtype, CL)
-    b = _run(case, *ops, dtype, CL)
-    for u, v, name in zip(a[1:], b[1:], ("out", "gx", "dgout", "dx")):
-        assert torch.equal(u, v), name
+    for case in ((8, 512, 4, 4, 1), CAPPED_CASE):
+        ops = _operands(case, dtype)
+        a = _run(case, *ops, dtype, CL)
+        b = _run(case, *ops, dtype, CL)
+        for u, v, name in zip(a[1:], b[1:], ("out", "gx", "dgout", "dx")):
+            assert torch.equal(u, v), (case, name)
 
 
 def test_third_order_request_raises():

@@ -51,16 +51,61 @@ def _ref(x, nz, nw, bias, gy):
     return dict(out=out, gx=gpre, gb=gpre.sum((0, 2, 3)), gnw=(gpre * nz).sum(), gnw_abs=(gpre * nz).abs().sum(), gn=gn)
 
 
-def _run(ops, dtype, fmt, nw=None):
+def _run(ops, dtype, fmt, nw=None, noise_grad=True, bias_grad=True):
+    """out and the gradients of the op on the device; a gradient that is not asked for (``noise_grad`` / ``bias_grad``) is None."""
     import ideas_amd.op as op
     x64, nz64, nw64, b64, gy64 = ops
     x = x64.to(dtype).cuda().contiguous(memory_format=fmt).requires_grad_(True)
-    nz = nz64.float().cuda().requires_grad_(True)
+    nz = nz64.float().cuda().requires_grad_(noise_grad)
     nwt = (nw64 if nw is None else nw).float().cuda().requires_grad_(True)
-    bias = b64.float().cuda().requires_grad_(True)
+    bias = b64.float().cuda().requires_grad_(bias_grad)
     out = op.noise_bias_act(x, nz, nwt, bias, SLOPE, SCALE)
-    gx, gn, gnw, gb = torch.autograd.grad(out, (x, nz, nwt, bias), gy64.to(dtype).cuda().contiguous(memory_format=fmt))
-    return dict(out=out.detach(), gx=gx, gn=gn, gnw=gnw, gb=gb)
+    leaves = {"gx": x, "gnw": nwt}
+    if noise_grad:
+        leaves["gn"] = nz
+    if bias_grad:
+        leaves["gb"] = bias
+    grads = torch.autograd.grad(out, list(leaves.values()), gy64.to(dtype).cuda().contiguous(memory_format=fmt))
+    res = dict(out=out.detach(), gn=None, gb=None)
+    res.update(zip(leaves, grads))
+    return res
+
+
+# Shapes past the grid caps (4096 blocks forward, NOISE_ACT_MAX_PARTIALS backward), so that a block takes its pixel loop more than
+# once, at both ends of the lane-group size: G = 64 (f32: 33 vectors of 4; bf16: 132 % 8 != 0, the scalar path with 132 elements
+# over 64 lanes, unevenly) and G = 4 (three scalar channels; a [1, 1, H, W] noise against B = 5: the fold through the workspace)
+MULTI_TRIP = (1, 132, 257, 257, 1)
+MULTI_TRIP_CASES = [MULTI_TRIP, (5, 3, 512, 512, 1)]
+# more than 64 vectors a pixel with lanes that carry different counts: 129 vectors of 4 f32 / of 8 bf16 (lane 0 three, the rest
+# two), 70 scalar elements (lanes 0..5 two, the rest one); each shape runs in both dtypes (516 bf16 and 70 are scalar paths)
+UNEVEN_CASES = [(2, 516, 3, 3, 2), (2, 1032, 3, 3, 2), (2, 70, 5, 5, 1)]
+
+
+def _trips(case, dtype):
+    """(forward, backward) passes of a block through its pixel loop, from the split csrc/noise_act.hip documents: L vectors of 4
+    f32 / 8 bf16 elements (elements when C is no multiple), G = the power of two >= min(L, 64) lanes a pixel, 256 / G pixels a block,
+    4 in flight; at most 4096 blocks forward and NOISE_ACT_MAX_PARTIALS backward."""
+    from ideas_amd import _lib
+    b, c, h, w, nb = case
+    vw = 8 if dtype == BF else 4
+    vectors = c // vw if c % vw == 0 else c
+    g = 1
+    while g < vectors and g < 64:
+        g *= 2
+    per_block, npix = (256 // g) * 4, b * h * w
+    trips = lambda cap: -(-npix // (min(-(-npix // per_block), cap) * per_block))
+    return trips(4096), trips(_lib.NOISE_ACT_MAX_PARTIALS)
+
+
+_case_cache = {}
+
+
+def _case(case, dtype):
+    """(operands, f64 reference) of a case, computed once."""
+    if (case, dtype) not in _case_cache:
+        ops = _operands(case, dtype)
+        _case_cache[(case, dtype)] = (ops, _ref(*ops))
+    return _case_cache[(case, dtype)]
 
 
 def _check_f32_side(case, got, ref):
@@ -76,12 +121,10 @@ def _check_f32_side(case, got, ref):
     assert d <= bound, (case, d, bound)
 
 
-@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
-@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
-def test_op_f32_vs_f64_restatement(case, fmt):
+def _check_f32(case, fmt):
     b, c, h, w, nb = case
-    ops = _operands(case, torch.float32)
-    got, ref = _run(ops, torch.float32, fmt), _ref(*ops)
+    ops, ref = _case(case, torch.float32)
+    got = _run(ops, torch.float32, fmt)
     assert tuple(got["out"].shape) == (b, c, h, w) and got["out"].dtype == torch.float32 and got["out"].is_contiguous(memory_format=CL)
     assert tuple(got["gn"].shape) == (nb, 1, h, w) and tuple(got["gnw"].shape) == (1,) and tuple(got["gb"].shape) == (c,)
     e = rel_err(got["out"], ref["out"])
@@ -93,11 +136,10 @@ def test_op_f32_vs_f64_restatement(case, fmt):
     _check_f32_side(case, got, ref)
 
 
-@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
-def test_op_bf16_vs_f64_on_the_same_operands(case):
+def _check_bf16(case):
     """bf16 tensors, channels_last: f32 arithmetic, one rounding to bf16 at each store; the f32 side results keep the f32 bounds."""
-    ops = _operands(case, BF)
-    got, ref = _run(ops, BF, CL), _ref(*ops)
+    ops, ref = _case(case, BF)
+    got = _run(ops, BF, CL)
     assert got["out"].dtype == BF and got["gx"].dtype == BF and got["gn"].dtype == torch.float32
     close_bf16(got["out"], ref["out"], "out")
     # the kernel's mask is the sign of the STORED bf16 output, which is the sign of the pre-activation
@@ -105,11 +147,66 @@ def test_op_bf16_vs_f64_on_the_same_operands(case):
     _check_f32_side(case, got, ref)
 
 
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
+def test_op_f32_vs_f64_restatement(case, fmt):
+    _check_f32(case, fmt)
+
+
+@pytest.mark.parametrize("case", OP_CASES, ids=_ids)
+def test_op_bf16_vs_f64_on_the_same_operands(case):
+    _check_bf16(case)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", [(2, 8, 9, 9, 2), (1, 5, 4, 4, 1), (2, 64, 33, 33, 2)], ids=_ids)
+@pytest.mark.parametrize("case", MULTI_TRIP_CASES, ids=_ids)
+def test_op_multi_trip_vs_f64(case, dtype):
+    """Capped grids: the grid-stride loops of both kernels, the shared trip count of the backward and a partial last trip."""
+    fwd, bwd = _trips(case, dtype)
+    print(case, dtype, "trips forward", fwd, "backward", bwd)
+    assert fwd >= 2 and bwd >= 2, (fwd, bwd)
+    if dtype == BF:
+        _check_bf16(case)
+    else:
+        _check_f32(case, CL)
+
+
+@pytest.mark.parametrize("fmt", [torch.contiguous_format, CL], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("case", UNEVEN_CASES, ids=_ids)
+def test_op_f32_uneven_lanes_above_64_vectors(case, fmt):
+    _check_f32(case, fmt)
+
+
+@pytest.mark.parametrize("case", UNEVEN_CASES, ids=_ids)
+def test_op_bf16_uneven_lanes_above_64_vectors(case):
+    _check_bf16(case)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", [(2, 64, 33, 33, 2), MULTI_TRIP], ids=_ids)
+def test_backward_without_noise_or_bias_gradient(case, dtype):
+    """What training runs: the noise is drawn or a buffer (no noise gradient: the kernel variant that never reads the noise weight)
+    and, for a frozen bias, no bias gradient.  Everything else is the full run's bits; gbias (float atomics) keeps its bound."""
+    ops, ref = _case(case, dtype)
+    full = _run(ops, dtype, CL)
+    got = _run(ops, dtype, CL, noise_grad=False)
+    assert got["gn"] is None
+    for k in ("out", "gx", "gnw"):
+        assert torch.equal(got[k], full[k]), ("no noise gradient", k)
+    e = rel_err(got["gb"], ref["gb"])
+    print(case, dtype, "gbias without the noise gradient", e)
+    assert e < GTOL, (case, e)
+    got = _run(ops, dtype, CL, bias_grad=False)
+    assert got["gb"] is None
+    for k in ("out", "gx", "gnw", "gn"):
+        assert torch.equal(got[k], full[k]), ("no bias gradient", k)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", [(2, 8, 9, 9, 2), (1, 5, 4, 4, 1), (2, 64, 33, 33, 2), MULTI_TRIP], ids=_ids)
 def test_zero_noise_weight_is_fused_leaky_relu_bit_for_bit(case, dtype):
     import ideas_amd.op as op
-    ops = _operands(case, dtype)
+    ops, _ = _case(case, dtype)
     got = _run(ops, dtype, CL, nw=torch.zeros(1, dtype=torch.float64))
     x = ops[0].to(dtype).cuda().contiguous(memory_format=CL)
     want = op.fused_leaky_relu(x, ops[3].float().cuda(), SLOPE, SCALE)
@@ -117,9 +214,9 @@ def test_zero_noise_weight_is_fused_leaky_relu_bit_for_bit(case, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", [(2, 64, 33, 33, 2), (2, 12, 9, 9, 1)], ids=_ids)
+@pytest.mark.parametrize("case", [(2, 64, 33, 33, 2), (2, 12, 9, 9, 1), MULTI_TRIP], ids=_ids)
 def test_two_runs_are_bitwise_equal(case, dtype):
-    ops = _operands(case, dtype)
+    ops, _ = _case(case, dtype)
     a, b = _run(ops, dtype, CL), _run(ops, dtype, CL)
     for k in ("out", "gx", "gnw", "gn"):
         assert torch.equal(a[k], b[k]), k

@@ -32,6 +32,16 @@ namespace {
 constexpr int WP = 64;            // column pairs per block
 constexpr int WN = 64;            // output channels per block
 constexpr int XROW = 36;          // floats per row of the exchange buffer (32 + pad: conflict-free float4 reads)
+// Fewest 64 x 256 tiles for which ideas_b3_wino_fwd takes the 256-channel tile.  On 256 CUs, nt wide tiles cost 2 ceil(nt / 256)
+// rounds of the 128-channel tile's work against ceil(nt / 128): up to 128 tiles the narrow tile needs half the time, and wherever
+// the last round of wide tiles is at most half full ((nt - 1) % 256 < 128) it saves a whole round -- more than the 6-12 % the wide
+// tile gains until that round is one in sixteen (WINO_N256_ANY_TILES).  Measured at 64 x 64, 512 -> 512 (profiles/
+// wino_n256_layer_ab.txt): 128 tiles 0.77x, 192 1.08x, 256 1.05x, 320 0.85x, 384 0.92x, 512 1.07x, 768 1.06x.
+// WINO_N256_ANY_TILES comes from that round arithmetic; the probes around it agree (1088 tiles, last round a quarter full: 1.00x;
+// 2112 and 2176 tiles: 1.03x and 1.05x).  Every launch of the training step has a multiple of 256 tiles, which the first
+// condition admits on its own.
+constexpr int WINO_N256_MIN_TILES = 129;
+constexpr int WINO_N256_ANY_TILES = 2048;
 
 // ---------------------------------------------------------------------------------------------------------------
 // weights: element (n, ky, kx, c) at w[base + n*sn + ky*sky + kx*skx + c*sc]  ->  U planes [4][3][3*C/16][N][16] bf16
@@ -524,8 +534,17 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 3 : 1) void conv_b3_wino_kernel
 // is in flight for a whole chunk instead of one sub-step -- 242 registers, no spill, counted waits of vmcnt(17..18); 1.5-3 % SLOWER
 // on the 128..512-channel layers (same box: 227.7 -> 224.4, 273.9 -> 266.3, 299.7 -> 289.7 TFLOP/s).  The weight loads cost issue
 // slots and L2 bandwidth, not latency: one sub-step of prefetch distance already covers it.)
+// NB = channel blocks of 32 per wave and pair half: the tile is 64 pairs x NB * 64 channels, eight waves = 4 Winograd components x 2
+// channel halves of NB * 32 channels.
+//   NB = 2 (64 x 128): four accumulators per wave, two Stage sets, two whole weight sets, (TP = 32) two A fragment sets.
+//   NB = 4 (64 x 256, Cout % 256 == 0 and enough tiles, wino_choose below): eight accumulators = 128 registers.  The staged
+//          chunk (window loads, transform, split, LDS stores) and every A fragment read now feed 144 MFMAs of a wave instead of
+//          72, and the input is fetched Cout / 256 times instead of Cout / 128.  What pays for the accumulators: one Stage set,
+//          one A fragment set, and the weights in quarter-sets through a ring of two (243-256 registers, no scratch: the build
+//          fails otherwise, csrc/Makefile).  Patch geometry, LDS image, K order, plane-pair order, tile walk (tiles_n = Cout / 256)
+//          and epilogues (four exchange rounds over the same buffer instead of two) are unchanged and the results bitwise equal.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool SCALE, bool REFLECT, int TP>
+template <bool SCALE, bool REFLECT, int TP, int NB>
 __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restrict__ y, const float* __restrict__ x,
                                                                 const void* __restrict__ uplanes,
                                                                 const float* __restrict__ in_scale,
@@ -536,7 +555,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
     constexpr int TR = WP / TP;                 // output rows of the patch
     constexpr int SR = (TR + 2) * TP;           // staged pair-rows per chunk
     constexpr int PL = SR * ROWB;               // bytes per plane
-    constexpr int BN = 2 * WN;                  // channels per block
+    constexpr int BN = NB * WN;                 // channels per block: two channel halves of NB 32-channel blocks each
     constexpr int BUFB = 12 * PL;
     constexpr int XB = 2 * 4 * WP * XROW * 4;   // exchange buffer of the epilogue
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUFB > XB ? 2 * BUFB : XB];
@@ -587,7 +606,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
     const int a_lds = r * ROWB + ((kq * 8) ^ (((r >> 3) & 1) << 4));
 
     struct Stage { float4 d[4], s; };
-    Stage st0, st1;
+    Stage st0, st1;                              // (NB = 4 uses st0 alone)
     int k_ci = 0;
     auto gloadA = [&](Stage& st) {
         const unsigned so = (unsigned)k_ci * 4u;
@@ -626,7 +645,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
     const int lane = t & 63, wave = t >> 6;
     const int wv = wave & 3, wh = wave >> 2;
     const int li = lane & 31, lh = lane >> 5;
-    f32x16 acc[2][2];
+    f32x16 acc[2][NB];
     // operand rows of sub-step ky: a*32 + ky*TP + li; the swizzle bit is bit 3 of that row (TP is a multiple of 8)
     int f_off[3];
 #pragma unroll
@@ -655,6 +674,26 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a][PA[q]], fb.f[b][PB[q]], acc[a][b], 0, 0, 0);
+    };
+    // NB = 4: the wave's twelve weight registers of a sub-step come as four QUARTER-SETS (one 32-channel block x 3 planes) through a
+    // ring of NQB register sets, each fetched NQB - 1 quarters (12 MFMAs each) ahead of the MFMAs that read it: 128 accumulator
+    // registers leave no room for two whole sets.  Per accumulator the products and their order are those of the 128-channel tile.
+    constexpr int NQB = 2;
+    struct BQuarter { bf16x8 f[3]; };
+    auto gloadBq = [&](BQuarter& fq, int b) {
+        const unsigned soff = (unsigned)(b_step * p.Cout) * 32u;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+            fq.f[pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                ru, (int)(fb_voff + (unsigned)pl * plane_bytes + (unsigned)(b * 32 * 32)), (int)soff, 0));
+        if (b == 3) ++b_step;
+    };
+    auto mfmas_q = [&](const bf16x8 (&fa)[2][3], const BQuarter& fq, int b) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+                acc[a][b % NB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a][PA[q]], fq.f[PB[q]], acc[a][b % NB], 0, 0, 0);
     };
     auto afrags = [&](const unsigned char* base, int ky, bf16x8 (&fa)[2][3]) {
 #pragma unroll
@@ -723,15 +762,40 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
         __builtin_amdgcn_sched_barrier(0);
         mfmas(faX, fbA);
     };
+    // NB = 4 (any TP): 128 accumulator registers leave room for ONE Stage set and one A fragment set.  The window of chunk c + 2 is
+    // fetched into the Stage registers right after chunk c + 1's has been transformed out of them (it still has most of a chunk to
+    // arrive); on entry the ring holds the first NQB - 1 quarters of the chunk.  A chunk is 12 quarters, a multiple of NQB, so the
+    // ring positions are the same in every chunk.
+    BQuarter fq[NQB];
+    auto step4 = [&](int c, Stage& st) {
+        const unsigned char* base = smem + (c & 1) * BUFB;
+        bf16x8 fa[2][3];
+#pragma unroll
+        for (int s = 0; s < 12; ++s) {
+            gloadBq(fq[(s + NQB - 1) % NQB], (s + NQB - 1) % 4);
+            if (s % 4 == 0) afrags(base, s / 4, fa);
+            if (s == 0) lstoreA((c & 1) ^ 1, transform_split(st));
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas_q(fa, fq[s % NQB], s % 4);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s == 0) gloadA(st);
+        }
+        __syncthreads();
+    };
     const int nc = p.Cin / BK;
     BFrag fb0, fb1;
     auto begin_tile = [&](int d) {                         // tile d: addresses, then its first window and weight loads
         set_tile(d);
-        fb_voff = (unsigned)((n0 + wh * 64 + li) * 32 + lh * 16) + (unsigned)(wv * 3) * plane_bytes;
+        fb_voff = (unsigned)((n0 + wh * (NB * 32) + li) * 32 + lh * 16) + (unsigned)(wv * 3) * plane_bytes;
         k_ci = 0;
         b_step = 0;
         gloadA(st0);
-        gloadB(fb0);
+        if constexpr (NB == 4) {
+#pragma unroll
+            for (int i = 0; i < NQB - 1; ++i) gloadBq(fq[i], i);
+        } else {
+            gloadB(fb0);
+        }
     };
     float* exch = reinterpret_cast<float*>(smem);
     const bool vec = wino_vec_ok(y, resid, out_scale, bias, p.Cout);
@@ -742,14 +806,16 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+        for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
     lstoreA(0, transform_split(st0));
-    gloadA(st1);
+    if constexpr (NB == 4) gloadA(st0); else gloadA(st1);
     __syncthreads();
     int c = 0;
-    if constexpr (TP == 32) {
+    if constexpr (NB == 4) {
+        for (; c < nc; ++c) step4(c, st0);
+    } else if constexpr (TP == 32) {
         bf16x8 faP[2][3], faQ[2][3];
         afrags(smem, 0, faP);
         for (; c + 1 < nc; c += 2) {
@@ -773,7 +839,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
     const bool more = d < ntiles;
     if (more) begin_tile(d);
 #pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
+    for (int hb = 0; hb < NB; ++hb) {
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -782,7 +848,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
         __syncthreads();
         if (epi != EPI_GENERIC) {
             // (the launcher checked: 16-byte addressable rows, Cout % 4 == 0, y below 4 GB, 0 <= alpha <= 1, no accumulate)
-            const int n = e_n0 + eh * 64 + hb * 32 + cg * 8;
+            const int n = e_n0 + eh * (NB * 32) + hb * 32 + cg * 8;
             if (n < p.Cout) {
                 const float* ex = exch + (eh * 4 * WP + er) * XROW + cg * 8;
                 const unsigned yoff = (unsigned)(opix + n) * 4u, pxs = (unsigned)p.Cout * 4u;
@@ -801,7 +867,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const int cl = cg * 8 + g * 4;
-            const int n = e_n0 + eh * 64 + hb * 32 + cl;
+            const int n = e_n0 + eh * (NB * 32) + hb * 32 + cl;
             if (n < p.Cout) {
                 const float* ex = exch + (eh * 4 * WP + er) * XROW + cl;
                 const float4 m0v = *reinterpret_cast<const float4*>(ex + 0 * WP * XROW);
@@ -846,21 +912,56 @@ extern "C" int ideas_b3_wino_split_weights(void* planes, const void* w, int N, i
     return ideas_launch_status();
 }
 
+// The ONE place that chooses among the Winograd kernels of a forward: ideas_b3_wino_fwd launches what this says, and the
+// diagnostic query below reports it.
+//   wide : 8-wave 64 x 128 tile, K-step 32 (else the 4-wave 64 x 64 tile)
+//   tp   : pair columns of the row-sharing kernel's patch when it applies (IDEAS_B3_WINO2D=0: never), else 0
+//   nt256: number of 64 x 256 tiles when the row-sharing kernel takes its 256-channel tile, else 0: Cout a multiple of 256 and a
+//          tile count at which the persistent grid still fills the chip (WINO_N256_MIN_TILES above).  IDEAS_B3_WINO_N256, read per
+//          call: "0" keeps the 128-channel tile; a positive number n is a rule of one's own, "at least n tiles" ("1": wherever
+//          Cout allows -- how the tests reach the tile on launches of a few tiles); unset or empty = the default rule.
+// The two tiles give bitwise equal results.
+struct WinoChoice { bool wide; int tp; int64_t nt256; };
+static WinoChoice wino_choose(int B, int IH, int IW, int Cin, int Cout) {
+    WinoChoice c;
+    c.wide = Cin % 32 == 0 && Cout > 64;
+    c.tp = 0;
+    c.nt256 = 0;
+    const char* e2d = getenv("IDEAS_B3_WINO2D");           // read per call: tests toggle it in-process
+    const int W2 = IW / 2;
+    const int TPsel = (W2 % 32 == 0) ? 32 : (W2 % 16 == 0) ? 16 : (W2 % 8 == 0) ? 8 : 0;
+    if (!c.wide || (e2d && e2d[0] == '0') || !TPsel || IH % (WP / TPsel) != 0) return c;
+    c.tp = TPsel;
+    if (Cout % (4 * WN) != 0) return c;
+    const int64_t nt = ideas_cdiv((int64_t)B * IH * W2, WP) * (Cout / (4 * WN));
+    const char* e256 = getenv("IDEAS_B3_WINO_N256");
+    bool take;
+    if (e256 && e256[0]) {
+        const long min_tiles = atol(e256);
+        take = min_tiles > 0 && nt >= min_tiles;
+    } else {
+        take = nt >= WINO_N256_MIN_TILES && ((nt - 1) % 256 >= 128 || nt >= WINO_N256_ANY_TILES);
+    }
+    c.nt256 = take ? nt : 0;
+    return c;
+}
+// (for tests and A/B scripts: the 64 x 256 tiles ideas_b3_wino_fwd runs on this shape under the present environment, 0 = another
+// tile; a diagnostic that is not part of the ABI of include/ideas_hip.h and not bound by ideas_amd/_lib.py)
+extern "C" int64_t ideas_b3_wino_n256_tiles(int B, int IH, int IW, int Cin, int Cout) { return wino_choose(B, IH, IW, Cin, Cout).nt256; }
+
 // called by ideas_conv3x3_wino for dtype IDEAS_F32_B3 (umat = planes of ideas_b3_wino_split_weights)
 int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* in_scale, const float* out_scale,
                       const float* bias, const void* resid, const ideas_conv_params* p, hipStream_t stream) {
     const int64_t M = (int64_t)p->B * p->IH * (p->IW / 2);
     const int64_t tm = ideas_cdiv(M, WP);
-    const bool wide = p->Cin % 32 == 0 && p->Cout > 64;     // 8-wave 64 x 128 tile, K-step 32
+    const WinoChoice ch = wino_choose(p->B, p->IH, p->IW, p->Cin, p->Cout);
+    const bool wide = ch.wide;                              // 8-wave 64 x 128 tile, K-step 32
     const int tn = (int)ideas_cdiv(p->Cout, wide ? 2 * WN : WN);
     if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
     const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
     const unsigned plane_bytes = (unsigned)((int64_t)3 * p->Cin * p->Cout * 2);     // one (v, plane): 3*Cin/16 steps x Cout x 32 B
     // row-sharing patch kernel: 8-wave tile shapes whose image divides into TR x TP patches (IDEAS_B3_WINO2D=0: the kernel above)
-    const char* e2d = getenv("IDEAS_B3_WINO2D");           // read per call: tests toggle it in-process
-    const bool use2d = !(e2d && e2d[0] == '0');
-    const int W2 = p->IW / 2;
-    const int TPsel = (W2 % 32 == 0) ? 32 : (W2 % 16 == 0) ? 16 : (W2 % 8 == 0) ? 8 : 0;
+    const int TPsel = ch.tp;
     // epilogue configuration (wino_finish_fast): IDEAS_B3_WINO_EPI=0 keeps the flag-testing tail everywhere (A/B measurements)
     int epi = EPI_GENERIC;
     {
@@ -873,23 +974,29 @@ int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* 
             else if (ba && resid && out_scale) epi = EPI_OS_BA_RS;
         }
     }
-    if (wide && use2d && TPsel && p->IH % (WP / TPsel) == 0 && p->Cin % 16 == 0) {
-        auto go2 = [&](auto sc, auto rf, auto tp) {
-            const int64_t nt = tm * tn;                       // persistent: one block per CU (98 KB of LDS each), a multiple of 8
+    if (TPsel) {
+        const bool n256 = ch.nt256 > 0;                      // 64 x 256 tile (NB = 4)
+        const int64_t nt = n256 ? ch.nt256 : tm * tn;
+        auto go2 = [&](auto sc, auto rf, auto tp, auto nb) {
+            // persistent: one block per CU (98 KB of LDS each), a multiple of 8
             const unsigned grid = (unsigned)(nt < 256 ? nt : 256);
-            hipLaunchKernelGGL((conv_b3_wino2d_kernel<decltype(sc)::value, decltype(rf)::value, decltype(tp)::value>),
+            hipLaunchKernelGGL((conv_b3_wino2d_kernel<decltype(sc)::value, decltype(rf)::value, decltype(tp)::value, decltype(nb)::value>),
                                dim3(grid), dim3(512), 0, stream, (float*)y, (const float*)x, uplanes, in_scale, out_scale,
-                               bias, (const float*)resid, *p, tn, x_bytes, plane_bytes, (int)nt, epi);
+                               bias, (const float*)resid, *p, (int)ideas_cdiv(p->Cout, decltype(nb)::value * WN),
+                               x_bytes, plane_bytes, (int)nt, epi);
         };
         using T = std::true_type;
         using F = std::false_type;
-        auto go1 = [&](auto tp) {
-            if (in_scale) { if (p->reflect) go2(T{}, T{}, tp); else go2(T{}, F{}, tp); }
-            else { if (p->reflect) go2(F{}, T{}, tp); else go2(F{}, F{}, tp); }
+        auto go1 = [&](auto tp, auto nb) {
+            if (in_scale) { if (p->reflect) go2(T{}, T{}, tp, nb); else go2(T{}, F{}, tp, nb); }
+            else { if (p->reflect) go2(F{}, T{}, tp, nb); else go2(F{}, F{}, tp, nb); }
         };
-        if (TPsel == 32) go1(std::integral_constant<int, 32>{});
-        else if (TPsel == 16) go1(std::integral_constant<int, 16>{});
-        else go1(std::integral_constant<int, 8>{});
+        auto go0 = [&](auto tp) {
+            if (n256) go1(tp, std::integral_constant<int, 4>{}); else go1(tp, std::integral_constant<int, 2>{});
+        };
+        if (TPsel == 32) go0(std::integral_constant<int, 32>{});
+        else if (TPsel == 16) go0(std::integral_constant<int, 16>{});
+        else go0(std::integral_constant<int, 8>{});
         return ideas_launch_status();
     }
     auto go = [&](auto sc, auto rf) {

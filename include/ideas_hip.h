@@ -14,8 +14,12 @@
  *   - no global state, no allocation, no host synchronisation: every call only enqueues on `stream`.  The only thing a call reads
  *     besides its arguments is a handful of A/B measurement switches in the process environment, looked up PER CALL (nothing is
  *     cached in the library): IDEAS_B3_WINO2D, IDEAS_B3_TPHASE, IDEAS_B3_WGRAD3, IDEAS_B3_WGRAD3_S2, IDEAS_S2FIR_CFG,
- *     IDEAS_BF16_IMG, IDEAS_BF16_WGRAD3, IDEAS_B3_PW, IDEAS_B3_PW_WGRAD, IDEAS_BF16_PW, IDEAS_B3_WINO_EPI, IDEAS_S2IMG_MIN_BLOCKS
- *     -- each "0" selects the older kernel of its family, unset = the default dispatch.
+ *     IDEAS_BF16_IMG, IDEAS_BF16_WGRAD3, IDEAS_B3_PW, IDEAS_B3_PW_WGRAD, IDEAS_BF16_PW, IDEAS_B3_WINO_EPI, IDEAS_S2IMG_MIN_BLOCKS,
+ *     IDEAS_B3_WINO_N256 -- each "0" selects the older kernel of its family, unset = the default dispatch; the *_MIN_BLOCKS
+ *     variable and IDEAS_B3_WINO_N256 also take a number.
+ *     (IDEAS_B3_WINO_N256: "0" keeps the 64 x 128 tile of the row-sharing Winograd kernel where Cout % 256 == 0; a positive number
+ *     n replaces the default tile-count rule by "at least n tiles of 64 x 256" (1: wherever Cout allows).  A diagnostic query beside this ABI, defined next to the
+ *     dispatch in csrc/conv_b3_wino.hip, tells tests and A/B scripts which tile a forward of a given shape takes.)
  *     What IS memoised per process: immutable device properties (the CU count and the occupancy hipOccupancy... reports for the
  *     library's own split-K kernels), used to size grids;
  *   - return value: 0 = enqueued; negative = argument error (IDEAS_E_*); positive = hipError_t of the launch.

@@ -77,6 +77,7 @@ class LinearSeg(C.Structure):
 LINEAR_MAX_SEGMENTS = 32
 MBSTD_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_MBSTD_MAX_PARTIALS
 NOISE_ACT_MAX_PARTIALS = 2048     # include/ideas_hip.h::IDEAS_NOISE_ACT_MAX_PARTIALS
+LPIPS_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_LPIPS_MAX_PARTIALS
 
 _P = C.c_void_p
 _PROTOS = {
@@ -144,6 +145,10 @@ _PROTOS = {
     "ideas_affine_warp": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P]),
     "ideas_affine_warp_bwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 9 + [_P]),
     "ideas_color_affine": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
+    "ideas_maxpool2x2_fwd": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
+    "ideas_maxpool2x2_bwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
+    "ideas_lpips_layer_fwd": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
+    "ideas_lpips_layer_bwd": (C.c_int, [_P] * 6 + [C.c_int] * 5 + [_P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

@@ -148,7 +148,10 @@ def _prefill(spans=None) -> None:
         return
     import bisect
     from .. import _lib
-    dead = [k for k, (_, ref, p0) in _RECORDED.items() if ref() is None or ref().data_ptr() != p0]
+    # strong references for the duration of the call: a parameter that is only kept alive by a reference cycle may be collected
+    # by any allocation below, between this liveness check and _prep_state's use of the same weak reference
+    bases = {k: ref() for k, (_, ref, _p0) in _RECORDED.items()}
+    dead = [k for k, b in bases.items() if b is None or b.data_ptr() != _RECORDED[k][2]]
     if dead:
         for k in dead:
             del _RECORDED[k]

@@ -490,6 +490,34 @@ int ideas_affine_warp_bwd(float* gx, const void* gy, const float* theta, int B, 
 int ideas_color_affine(void* y, const void* x, const float* m, int B, int H, int W, int layout, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LPIPS (VGG): the 2x2 max pool of the backbone and the per-layer head of the learned perceptual distance
+ * (stylegan2/lpips/networks_basic.py:64-92, spatial=False, lpips=True), csrc/lpips.hip.
+ * Every tensor is [B,H,W,C] channels-innermost, f32 or bf16 with f32 arithmetic and one rounding at the store.
+ *   ideas_maxpool2x2_fwd   y [B,H/2,W/2,C] (floor): window 2x2, stride 2, no padding; an odd trailing row / column is in no window.
+ *   ideas_maxpool2x2_bwd   gx [B,H,W,C] from gy and the saved input x: gy at the window's maximum, 0 elsewhere, every element of gx
+ *                          written exactly once (no memset, no atomics).  Ties go to the first element of the window in row-major
+ *                          order; a NaN counts as the maximum (torch's max_pool2d).
+ *   ideas_lpips_layer_fwd  f0, f1 [B,H,W,C], w float[C]; d float[B]:
+ *                              n_i[p] = sqrt(sum_c f_i[p,c]^2);  u_i = f_i / (n_i + 1e-10)
+ *                              d[b]   = (1/(H W)) sum_p sum_c w[c] (u_0[p,c] - u_1[p,c])^2
+ *                          workspace: B * IDEAS_LPIPS_MAX_PARTIALS doubles, overwritten (one double per block and sample, added in
+ *                          index order by a second small kernel: no floating-point atomics).
+ *   ideas_lpips_layer_bwd  gd float[B]; gf0 / gf1 [B,H,W,C], either may be NULL (that gradient is not wanted), not both:
+ *                              g_c   = 2 w_c (u_0c - u_1c) gd[b] / (H W)
+ *                              gf0_k = g_k / (n_0 + eps) - f0_k (sum_c g_c f0_c) / (n_0 (n_0 + eps)^2);   gf1: the mirror image, negated
+ *                          A pixel with n_i = 0 (all features zero) gets gf_i = 0.
+ * 16-byte vectors along C when C % 4 == 0 (% 8 for bf16) and every pointer is 16-byte aligned, an element-wise path otherwise.
+ * All four are bitwise reproducible.  The head keeps a pixel of both tensors in registers: C <= 2048 (IDEAS_E_UNSUPPORTED above).
+ * IDEAS_E_SHAPE: a non-positive size, H < 2 or W < 2 for the pool, B > 65535 for the head.  (Additive within ABI 4.) */
+#define IDEAS_LPIPS_MAX_PARTIALS 64
+int ideas_maxpool2x2_fwd(void* y, const void* x, int B, int C, int H, int W, int dtype, void* stream);
+int ideas_maxpool2x2_bwd(void* gx, const void* gy, const void* x, int B, int C, int H, int W, int dtype, void* stream);
+int ideas_lpips_layer_fwd(float* d, void* workspace, const void* f0, const void* f1, const float* w, int B, int C, int H, int W,
+                          int dtype, void* stream);
+int ideas_lpips_layer_bwd(void* gf0, void* gf1, const float* gd, const void* f0, const void* f1, const float* w, int B, int C, int H,
+                          int W, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

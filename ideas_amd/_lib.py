@@ -78,6 +78,8 @@ LINEAR_MAX_SEGMENTS = 32
 MBSTD_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_MBSTD_MAX_PARTIALS
 NOISE_ACT_MAX_PARTIALS = 2048     # include/ideas_hip.h::IDEAS_NOISE_ACT_MAX_PARTIALS
 LPIPS_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_LPIPS_MAX_PARTIALS
+POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1_VALID = 0, 1, 2     # include/ideas_hip.h::IDEAS_POOL_*
+FEATURE_STATS_MAX_DIM = 4096     # include/ideas_hip.h::IDEAS_FEATURE_STATS_MAX_DIM
 
 _P = C.c_void_p
 _PROTOS = {
@@ -149,6 +151,9 @@ _PROTOS = {
     "ideas_maxpool2x2_bwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_lpips_layer_fwd": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
     "ideas_lpips_layer_bwd": (C.c_int, [_P] * 6 + [C.c_int] * 5 + [_P]),
+    "ideas_pool3x3_fwd": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "ideas_global_avg_pool": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
+    "ideas_feature_stats_accum": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

@@ -85,8 +85,48 @@ class LMDBDataset(data.Dataset):
         return _decode(Image.open(BytesIO(img_bytes)), self.resolution)
 
 
+class MultiResolutionDataset(data.Dataset):
+    """The multi-resolution LMDB that stylegan2/prepare_data.py writes and stylegan2/calc_inception.py reads (stylegan2/dataset.py:8-40):
+    ``length`` holds the number of images, ``<resolution>-<index, five digits>`` the encoded image at that resolution (stored at its
+    size: nothing is resized here).  Hands out uint8 [R, R, 3] like the other datasets; needs the ``lmdb`` package."""
+
+    def __init__(self, path: str, resolution: int = 256, max_num: Optional[int] = None):
+        try:
+            import lmdb
+        except ImportError as e:   # pragma: no cover - depends on the image
+            raise ImportError("MultiResolutionDataset needs the 'lmdb' package; use dataset_type='normal'") from e
+        self.env = lmdb.open(path, max_readers=32, readonly=True, lock=False, readahead=False, meminit=False)
+        if not self.env:
+            raise IOError('Cannot open lmdb dataset', path)
+        with self.env.begin(write=False) as txn:
+            length = txn.get(b"length")
+        if length is None:
+            raise IOError(f"{path}: no 'length' entry (not a stylegan2 multi-resolution lmdb)")
+        self.length = int(length.decode("utf-8"))
+        if max_num is not None:
+            self.length = min(self.length, max_num)
+        self.resolution = resolution
+
+    def __len__(self) -> int:
+        return self.length
+
+    def __getitem__(self, index: int) -> torch.Tensor:
+        from PIL import Image
+        key = f"{self.resolution}-{str(index).zfill(5)}".encode("utf-8")
+        with self.env.begin(write=False) as txn:
+            img_bytes = txn.get(key)
+        if img_bytes is None:
+            raise KeyError(f"no image {key.decode()} (was the lmdb prepared at resolution {self.resolution}?)")
+        arr = np.asarray(Image.open(BytesIO(img_bytes)).convert("RGB"), dtype=np.uint8)
+        if arr.shape[:2] != (self.resolution, self.resolution):
+            raise ValueError(f"image {key.decode()} is {arr.shape[1]}x{arr.shape[0]}, not {self.resolution}x{self.resolution}")
+        return torch.from_numpy(arr.copy())
+
+
 def set_dataset(type: str, path: str, resolution: int, max_num: int = 70000) -> data.Dataset:
-    """dataset.py:76-85 (the transform argument is gone: it runs on the device)."""
+    """dataset.py:76-85 (the transform argument is gone: it runs on the device), plus ``multires``: stylegan2's own LMDB layout."""
+    if type == 'multires':
+        return MultiResolutionDataset(path, resolution, max_num)
     if type == 'lmdb':
         return LMDBDataset(path, resolution, max_num)
     if type == 'normal':

@@ -69,11 +69,11 @@ def wino_weights(w_ohwi: torch.Tensor) -> torch.Tensor:
 def _wino_ok(g: "ConvGeom", cin: int, width: int, fwd: bool = True) -> bool:
     if fwd and MATH == _lib.F32_B3 and cin % 16 == 0:
         return False          # the split-bf16 direct kernel outruns the f32 Winograd kernel
-    return WINOGRAD and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and width % 2 == 0 and cin % 8 == 0
+    return WINOGRAD and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and not g.rect and width % 2 == 0 and cin % 8 == 0
 
 
 def _b3_wino_ok(g: "ConvGeom", cin: int, cout: int, width: int) -> bool:
-    return (MATH == _lib.F32_B3 and B3_WINO and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and width % 2 == 0
+    return (MATH == _lib.F32_B3 and B3_WINO and g.kh == 3 and g.kw == 3 and g.stride == 1 and g.pad == 1 and not g.rect and width % 2 == 0
             and cin % 16 == 0 and cout % 4 == 0)
 
 
@@ -580,6 +580,23 @@ def fork_conv2d(input: torch.Tensor, weight: torch.Tensor, padding: int = 0, gai
     return _ForkConv.apply(to_act(input), weight, g, float(gain))
 
 
+def _geom(weight: torch.Tensor, stride: int, padding, reflect: bool, *grad_of) -> ConvGeom:
+    """The geometry of ``conv2d`` / ``conv2d_bias_act``: ``padding`` an int or an ``(ph, pw)`` pair.  ``ph != pw`` is forward-only
+    (the generic implicit-GEMM kernels): mirror padding and anything that asks for a gradient raise."""
+    if isinstance(padding, (tuple, list)):
+        if len(padding) != 2:
+            raise RuntimeError(f"padding must be an int or an (ph, pw) pair, got {padding!r}")
+        g = ConvGeom(weight.shape[2], weight.shape[3], stride, int(padding[0]), reflect, int(padding[1]))
+    else:
+        g = ConvGeom(weight.shape[2], weight.shape[3], stride, int(padding), reflect)
+    if g.rect:
+        if reflect:
+            raise RuntimeError("mirror padding takes one padding for both axes")
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in grad_of):
+            raise RuntimeError(conv_plan.RECT_GRAD_MSG)
+    return g
+
+
 class _AddBias(Function):
     """y + bias[c] with the bias gradient on ``ideas_channel_sum`` (autograd's sum over (0, 2, 3) of a channels_last tensor with
     C = 3 ran as ONE block: 1.0 ms per G.to_rgb backward).  Under create_graph the backward is the differentiable composite.
@@ -606,11 +623,12 @@ class _AddBias(Function):
 
 
 def conv2d(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1,
-           padding: int = 0, reflect: bool = False, gain: float = 1.0, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+           padding=0, reflect: bool = False, gain: float = 1.0, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``gain * F.conv2d(input, weight, stride, padding) + bias`` (zero padding, or mirror padding if ``reflect``);
+    ``padding``: an int or an ``(ph, pw)`` pair (``ph != pw``: forward-only);
     ``resid``: a tensor of the output's shape added in the conv epilogue (differentiable)."""
     _lib.require_cuda(input, weight, bias)
-    g = ConvGeom(weight.shape[2], weight.shape[3], stride, padding, reflect)
+    g = _geom(weight, stride, padding, reflect, input, weight, resid)
     if resid is not None:
         if bias is not None:
             raise RuntimeError("conv2d(resid=...) with a conv bias is not used on this path")
@@ -848,17 +866,20 @@ def down_pair(input: torch.Tensor, w1, b1, w2, b2, fir, pad2, padding1: int = 1,
                            (int(pad2[0]), int(pad2[1])), float(gain2), float(negative_slope), float(scale2))
 
 
-def conv2d_bias_act(input: torch.Tensor, weight: torch.Tensor, act_bias: torch.Tensor, stride: int = 1, padding: int = 0,
+def conv2d_bias_act(input: torch.Tensor, weight: torch.Tensor, act_bias: torch.Tensor, stride: int = 1, padding=0,
                     reflect: bool = False, gain: float = 1.0, negative_slope: float = 0.2,
                     scale: float = 2 ** 0.5, resid: Optional[torch.Tensor] = None, post_blur=None) -> torch.Tensor:
     """``fused_leaky_relu(gain * conv2d(input, weight), act_bias, negative_slope, scale)`` in one kernel.
+    ``padding``: an int or an ``(ph, pw)`` pair (``ph != pw``: forward-only, on the generic implicit-GEMM kernels).
     ``resid`` (inference only): the residual branch, added in the same epilogue.
     ``post_blur = (fir, (pad0, pad1))``: also apply ``upfirdn2d(., fir, pad=pad)`` to the result (the Blur of the next, downsampling,
     layer) so that the backward can fuse the blur's adjoint with the activation's (``_ConvBiasActBlur``)."""
     _lib.require_cuda(input, weight, act_bias)
-    g = ConvGeom(weight.shape[2], weight.shape[3], stride, padding, reflect)
+    g = _geom(weight, stride, padding, reflect, input, weight, act_bias)
     input = to_act(input)
     if post_blur is not None:
+        if g.rect:
+            raise RuntimeError("conv2d_bias_act: post_blur takes one padding for both axes")
         if resid is not None:
             raise RuntimeError("conv2d_bias_act: post_blur and resid are exclusive")
         fir, pad2 = post_blur

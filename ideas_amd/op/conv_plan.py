@@ -32,9 +32,25 @@ class ConvGeom:
     stride: int = 1
     pad: int = 0
     reflect: bool = False
+    pad_w: Optional[int] = None      # horizontal padding where it differs from ``pad`` (then the vertical one); None = ``pad``
+
+    def __post_init__(self):
+        if self.pad_w is not None and self.pad_w == self.pad:     # one spelling per geometry: equal paddings compare (and hash) equal
+            object.__setattr__(self, "pad_w", None)
+
+    @property
+    def pw(self) -> int:
+        """The horizontal padding."""
+        return self.pad if self.pad_w is None else self.pad_w
+
+    @property
+    def rect(self) -> bool:
+        """Rectangular padding (the 1x7 / 7x1 / 1x3 / 3x1 layers of Inception-v3): the generic forward kernels only -- no Winograd,
+        blur fusion, mirror padding, transposed conv or gradient plan takes it."""
+        return self.pad_w is not None
 
     def out_size(self, ih: int, iw: int) -> Tuple[int, int]:
-        return ((ih + 2 * self.pad - self.kh) // self.stride + 1, (iw + 2 * self.pad - self.kw) // self.stride + 1)
+        return ((ih + 2 * self.pad - self.kh) // self.stride + 1, (iw + 2 * self.pw - self.kw) // self.stride + 1)
 
 
 @dataclass
@@ -324,12 +340,18 @@ def peek_on(w: torch.Tensor, key, t: torch.Tensor):
     return None if v is None else v[1]
 
 
+RECT_GRAD_MSG = ("a conv with rectangular padding (pad != pad_w) is forward-only: its input and weight gradients are not implemented "
+                 "(the layers that use it, Inception-v3's 1x7 / 7x1 / 1x3 / 3x1 convs, are frozen)")
+
+
 def plan_fwd(x_shape, w: torch.Tensor, g: ConvGeom) -> Launch:
+    if g.rect and g.reflect:
+        raise RuntimeError("mirror padding takes one padding for both axes (pad_w == pad)")
     b, ci, ih, iw = x_shape
     co = w.shape[0]
     oh, ow = g.out_size(ih, iw)
     return Launch(B=b, IH=ih, IW=iw, Cin=ci, YH=oh, YW=ow, Cout=co, OH=oh, OW=ow, TY=g.kh, TX=g.kw,
-                  sy=g.stride, sx=g.stride, dy=1, dx=1, offy=-g.pad, offx=-g.pad, reflect=int(g.reflect),
+                  sy=g.stride, sx=g.stride, dy=1, dx=1, offy=-g.pad, offx=-g.pw, reflect=int(g.reflect),
                   wview=w.permute(0, 2, 3, 1), wsrc=w, wkey=("fwd",))
 
 
@@ -342,6 +364,8 @@ def _phase(r: int, p: int, s: int, k: int):
 
 def plan_dgrad(gy_shape, w: torch.Tensor, g: ConvGeom, in_hw: Tuple[int, int]) -> Tuple[List[Launch], bool]:
     """Launches computing gx[B, I, IH, IW] from gy[B, O, OH, OW]; second value: must gx be pre-zeroed."""
+    if g.rect:
+        raise RuntimeError(RECT_GRAD_MSG)
     if g.reflect:
         raise ValueError("dgrad of a reflect-padded conv: compute the padded gradient (pad=0 geometry on the padded "
                          "size) and fold it with reflection_pad2d_backward")
@@ -371,6 +395,8 @@ def plan_dgrad(gy_shape, w: torch.Tensor, g: ConvGeom, in_hw: Tuple[int, int]) -
 
 def plan_wgrad(x_shape, gy_shape, g: ConvGeom) -> Launch:
     """gw[O, KH, KW, I] (OHWI) from x[B, I, IH, IW] and gy[B, O, OH, OW]."""
+    if g.rect:
+        raise RuntimeError(RECT_GRAD_MSG)
     b, ci, ih, iw = x_shape
     _, co, oh, ow = gy_shape
     return Launch(B=b, IH=ih, IW=iw, Cin=ci, YH=oh, YW=ow, Cout=co, OH=oh, OW=ow, TY=g.kh, TX=g.kw,
@@ -379,4 +405,6 @@ def plan_wgrad(x_shape, gy_shape, g: ConvGeom) -> Launch:
 
 def convT_out_size(ih: int, iw: int, g: ConvGeom) -> Tuple[int, int]:
     """Output size of conv_transpose2d(stride s, padding p): (ih-1)*s - 2p + kh."""
+    if g.rect:
+        raise RuntimeError("a transposed conv takes one padding for both axes (pad_w == pad)")
     return (ih - 1) * g.stride - 2 * g.pad + g.kh, (iw - 1) * g.stride - 2 * g.pad + g.kw

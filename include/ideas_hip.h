@@ -518,6 +518,31 @@ int ideas_lpips_layer_bwd(void* gf0, void* gf1, const float* gd, const void* f0,
                           int W, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FID Inception-v3 (stylegan2/inception.py): the 3x3 pools and the global average of the network, csrc/pool.hip, and the streaming
+ * f64 feature statistics of the Frechet distance (stylegan2/fid.py:97-98), csrc/feature_stats.hip.
+ *   ideas_pool3x3_fwd      x [B,H,W,C] channels-innermost, f32 or bf16 (f32 arithmetic, one rounding at the store); y by `mode`:
+ *       IDEAS_POOL_MAX_S2          F.max_pool2d(x, 3, 2): y [B,(H-3)/2+1,(W-3)/2+1,C], no padding (IDEAS_E_SHAPE for H < 3 or W < 3)
+ *       IDEAS_POOL_MAX_S1P1        F.max_pool2d(x, 3, 1, 1): y [B,H,W,C]; a padding tap never wins
+ *       IDEAS_POOL_AVG_S1P1_VALID  F.avg_pool2d(x, 3, 1, 1, count_include_pad=False): y [B,H,W,C]; the divisor is the number of
+ *                                  in-image taps (4 at corners, 6 at edges, 9 inside); f32 sum in a fixed tap order
+ *     In the max modes a NaN counts as the maximum (torch's max_pool2d).  16-byte vectors along C when C % 4 == 0 (% 8 for bf16) and
+ *     both pointers are 16-byte aligned, an element-wise path otherwise.
+ *   ideas_global_avg_pool  out float [B][C] = the mean over H W of x [B,H,W,C] (adaptive_avg_pool2d(x, 1)), f32 sum in index order.
+ *   ideas_feature_stats_accum  x float [N][D]; sum double [D] += sum_n x[n]; gram double [D][D] += x^T x, every product and sum in
+ *     f64.  The full matrix is written, symmetric by construction.  Any N >= 1, 1 <= D <= IDEAS_FEATURE_STATS_MAX_DIM
+ *     (IDEAS_E_UNSUPPORTED above).  Each element is owned by one thread which adds its N terms in index order to the value already
+ *     there: no atomics, and two updates are bitwise one update with the concatenated rows.
+ * All three are bitwise reproducible.  IDEAS_E_SHAPE: a non-positive size; IDEAS_E_UNSUPPORTED: a dtype other than f32 / bf16 or
+ * an unknown mode; every check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#define IDEAS_POOL_MAX_S2 0
+#define IDEAS_POOL_MAX_S1P1 1
+#define IDEAS_POOL_AVG_S1P1_VALID 2
+#define IDEAS_FEATURE_STATS_MAX_DIM 4096
+int ideas_pool3x3_fwd(void* y, const void* x, int B, int C, int H, int W, int mode, int dtype, void* stream);
+int ideas_global_avg_pool(float* out, const void* x, int B, int C, int H, int W, int dtype, void* stream);
+int ideas_feature_stats_accum(double* sum, double* gram, const float* x, int N, int D, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

@@ -219,6 +219,11 @@ class Generator(nn.Module):
                 inject_index = random.randint(1, self.n_latent - 1)
             latent = torch.cat([styles[0].unsqueeze(1).expand(-1, inject_index, -1),
                                 styles[1].unsqueeze(1).expand(-1, self.n_latent - inject_index, -1)], 1)
+        # A caller that asks for the latents while a graph is being built may differentiate the image with respect to them
+        # (g_path_regularize(fake_img, latents), stylegan2/train.py:252-255): the image is then computed from the returned
+        # [B, n_latent, D] tensor itself, layer i reading latent[:, i], as the reference does (model.py:560-571).
+        if shared is not None and return_latents and torch.is_grad_enabled() and shared.requires_grad:
+            shared = None
         if shared is not None:
             # all layers read the same latent: their modulations come from one batched launch (model.styles_for, keyed on the tensor)
             with styles_for(self._modconvs(), shared):

@@ -141,6 +141,47 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return a * b;
 }
 
+// One f32 subtract / multiply / FMA as ONE single-issue VALU instruction that the vectorisers cannot pair.  Written as plain C++, two
+// adjacent f32 subtractions (b3.hpp::split2) or multiplies (the modulation scale) are SLP-packed by -O3 into v_pk_add_f32 /
+// v_pk_mul_f32, and a packed f32 op issued beside MFMAs costs far more than its two halves (MI355X: two v_pk_add_f32 in an MFMA gap
+// +26 cycles against two scalar ones).  Same IEEE operation, same rounding and denormal mode: results are bitwise those of `a - b` /
+// `a * b`; the multiply cannot be contracted into an FMA, which keeps mul_rn's guarantee.  Not `volatile`: the compiler may still
+// move, merge or drop them.  -DIDEAS_B3_PACKED_F32=1 restores the plain operators (the packed form, for A/B builds).
+// RESTRICTION: the compiler's hazard recogniser does not look inside inline assembly (no wait states for MFMA -> VALU read / write of
+// the same registers, none for a VALU write that a DPP instruction reads next).  Use them only where they are used now: on staged
+// loads and on values computed from them, with results that feed v_cvt_pk_bf16_f32 / LDS stores / plain VALU code -- never on
+// MFMA results (an epilogue) and never on a value whose next reader is a DPP instruction (conv_b3_s2fir.hip::hrow1's source).
+#ifndef IDEAS_B3_PACKED_F32
+#define IDEAS_B3_PACKED_F32 0
+#endif
+__device__ __forceinline__ float sub1(float a, float b) {
+#if IDEAS_B3_PACKED_F32
+    return a - b;
+#else
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#endif
+}
+__device__ __forceinline__ float mul1(float a, float b) {
+#if IDEAS_B3_PACKED_F32
+    return mul_rn(a, b);
+#else
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#endif
+}
+__device__ __forceinline__ float fma1(float a, float b, float c) {      // fmaf(a, b, c)
+#if IDEAS_B3_PACKED_F32
+    return fmaf(a, b, c);
+#else
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#endif
+}
+
 // argument check shared by the convolution entry points (conv_direct.hip)
 int check_conv(const ideas_conv_params* p);
 

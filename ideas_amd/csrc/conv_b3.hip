@@ -30,6 +30,9 @@
 // 16-byte halves swapped on rows with bit 3 set: ds_write_b64 (staging), ds_write_b128 (weights) and the
 // ds_read_b128 operand fetch are all conflict-free (checked by enumeration against the bank rules of
 // MI355X_MICROARCH.md).  Lane (i = lane&31, h = lane>>5) of a 32x32x16 MFMA holds K values [8h, 8h+8) of row i.
+// (census with this file's packed f32 staging ops split into single instructions: no gain beyond the run-to-run spread,
+//  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
+#define B3_UNPACK_F32 0
 #include "b3.hpp"
 #include <type_traits>
 
@@ -226,7 +229,7 @@ __device__ __forceinline__ void conv_b3_body(float* __restrict__ y, const float*
         for (int j = 0; j < A_PER; ++j) {
             float4 v = st.a[j];
             // rounded to f32 BEFORE the split (no FMA contraction into the residual), as in the f32 kernel
-            if (SCALE) v = make_float4(mul_rn(v.x, st.s[j].x), mul_rn(v.y, st.s[j].y), mul_rn(v.z, st.s[j].z), mul_rn(v.w, st.s[j].w));
+            if (SCALE) v = b3_scale4(v, st.s[j]);
             const Split4 s = split4(v);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint2*>(base + a_lds[j] + pl * PLANE_A) = s.p[pl];

@@ -18,6 +18,9 @@
 //     return zeros (buffer bounds), the stores are dropped by the same bounds / an out-of-range offset.
 // Arithmetic, op order and epilogue (gain, bias, leaky-ReLU, residual) are those of conv_b3_kernel: each output is the same six
 // plane-pair MFMA chains over K in the same order, so results are BITWISE the generic kernel's (tests/test_ops_gpu.py).
+// (census with this file's packed f32 staging ops split into single instructions: no gain beyond the run-to-run spread,
+//  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
+#define B3_UNPACK_F32 0
 #include "b3.hpp"
 #include <cstdlib>
 

@@ -179,12 +179,16 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
             const float4 v = ldv[r % RING];
             h[r % 4] = make_float4(hrow1(v.x), hrow1(v.y), hrow1(v.z), hrow1(v.w));
         };
+        const float kv0 = f.kv[0], kv1 = f.kv[1], kv2 = f.kv[2], kv3 = f.kv[3];
         auto vsum1 = [&](float r0, float r1, float r2, float r3) {
             // blur4_f32_c2 writes r0 k0 + r1 k1 + r2 k2 + r3 k3, which hipcc contracts as fma(r0, k0, r1 k1) then the other two: same order here
-            float s_ = r1 * f.kv[1];
-            s_ = fmaf(r0, f.kv[0], s_);
-            s_ = fmaf(r2, f.kv[2], s_);
-            return fmaf(r3, f.kv[3], s_);
+            // (single-issue instructions, b3.hpp: left to itself -O3 packs the four channels of a pixel into v_pk_mul_f32 / v_pk_fma_f32
+            //  pairs, which beside the consumer waves' MFMAs cost the fused kernel 9 %: 25.2 -> 22.9 ms per step against the packed build,
+            //  profiles/unpack_f32_family_ab.txt section 3)
+            float s_ = b3_mul(r1, kv1);
+            s_ = b3_fma(r0, kv0, s_);
+            s_ = b3_fma(r2, kv2, s_);
+            return b3_fma(r3, kv3, s_);
         };
         // image row i (raw rows i .. i + 3 filtered): vertical sum, split, LDS store (+ side output)
         auto emit = [&](unsigned char* buf, int i, int ci_chunk, float4 sc) {
@@ -193,7 +197,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
                                          vsum1(r0.w, r1.w, r2.w, r3.w));
             Split4 s_;
             if constexpr (MOD) {                         // (in_scale is uniform: no divergence)
-                s_ = split4(in_scale ? make_float4(mul_rn(o.x, sc.x), mul_rn(o.y, sc.y), mul_rn(o.z, sc.z), mul_rn(o.w, sc.w)) : o);
+                s_ = split4(in_scale ? b3_scale4(o, sc) : o);
             } else {
                 s_ = split4(o);
             }
@@ -218,7 +222,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
         const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)in_scale, 0, ((MODE == 1 || MOD) && in_scale) ? p.B * p.Cin * 4 : 0, (int)RSRC_FLAGS);
         auto emit_plain = [&](unsigned char* buf, int i, float4 sc) {
             float4 v = ldv[i % RING];
-            if (in_scale) v = make_float4(mul_rn(v.x, sc.x), mul_rn(v.y, sc.y), mul_rn(v.z, sc.z), mul_rn(v.w, sc.w));
+            if (in_scale) v = b3_scale4(v, sc);
             const Split4 s_ = split4(v);
             if (on) {
                 unsigned char* a = buf + ((i & 1) ? (w0 ^ 16) : w0) + i * PITCH * ROWB;

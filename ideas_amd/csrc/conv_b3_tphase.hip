@@ -19,11 +19,16 @@
 //   B:     the per-phase weight planes of ideas_b3_split_weights_strided ([3][chunk * taps + tap][Cout][16] = the MFMA operand
 //          layout) are fetched straight from global memory one tap group ahead, as conv_b3_wino.hip does;
 //   LDS:   two buffers of 3 planes x 5 rows x 32 pixels x 32 B (30 KB; 17 pixels of a row in use); 16-byte halves of a pixel
-//          swapped on pixels with bit 3 set.
+//          swapped on pixels with bit 3 set.  The 16-byte-store epilogue (ST16) reuses them, 8 KB per wave (32 KB).
 // Requires the canonical pad-0 geometry of op/conv_plan.py::plan_dgrad (4 launches, taps 2x2 / 2x1 / 1x2 / 1x1, offsets 0,
 // tap step -1), Cin % 16 == 0, Cout > 64 (smaller layers keep conv_b3_multi_kernel).
+// (the single-issue staging ops of b3.hpp are on in this file FOR THE SPILL, not for speed: with the plain operators the modulated
+//  instantiation conv_b3_tphase_kernel<true, true> spills 20 bytes per lane, with the helpers none.  Measured, committed form
+//  against the packed build: conv_igemm_multi 44.84 / 44.92 -> 45.00 / 44.98 ms, 0.3 % SLOWER; profiles/unpack_f32_family_ab.txt,
+//  unpack_f32_isa_counts.txt)
 #include "b3.hpp"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -42,12 +47,15 @@ struct TPhase {
 };
 
 
-template <bool SCALE>
+template <bool SCALE, bool ST16>
 __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restrict__ y, const float* __restrict__ x,
                                                                 const float* __restrict__ in_scale,
                                                                 const float* __restrict__ out_scale, ideas_conv_params p, TPhase a,
                                                                 int QH, int QW, int tiles_n, unsigned x_bytes) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUFB];
+    // (ST16: the epilogue passes the accumulators through LDS, 4 waves x 8 KB = 32 KB per block against the 30 KB of the two staging
+    //  buffers: the ST16 instantiations allocate 32 KB, still two blocks per CU)
+    constexpr int EPIB = 4 * 64 * 32 * 4;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[ST16 && EPIB > 2 * BUFB ? EPIB : 2 * BUFB];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int ppr = (QW + PW - 1) / PW, ppi = ((QH + PH - 1) / PH) * ppr;
     const int swz = xcd_swizzle(blockIdx.x, gridDim.x);
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restric
         for (int j = 0; j < 2; ++j) {
             if (j == 1 && wave >= 2) break;
             float4 v = st.v[j];
-            if (SCALE) v = make_float4(mul_rn(v.x, st.s.x), mul_rn(v.y, st.s.y), mul_rn(v.z, st.s.z), mul_rn(v.w, st.s.w));
+            if (SCALE) v = b3_scale4(v, st.s);
             const Split4 s = split4(v);
             if (lds_st[j] >= 0) {
 #pragma unroll
@@ -217,6 +225,9 @@ __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restric
     // it read (128 KB), 64 MB per round of blocks = 4 TB/s, and nothing overlaps it -- without the stores the fixed cost is 2.7 us.
     // Tried and measured flat: a random start delay for the first round's blocks (de-phasing), nontemporal stores, and stores to one
     // contiguous 128 KB region per block (so it is not the 128-byte-per-KB pattern).  16-chunk layers run at 0.85 of the store-free rate.
+    // What did move it: 16 bytes per lane and store instruction (ST16 below; all of the above kept one dword per lane) -- the tail is
+    // bound by the ISSUE of 128 store instructions per wave, not by bandwidth.  Same process, interleaved, B = 32 / 96: 8-chunk layer
+    // 2.763 -> 2.315 ms, 16 chunks 1.527 -> 1.420, 32 chunks 1.419 -> 1.373 (profiles/tphase_store16_ab.txt).
     BSet b0, b1;
     gloadA();
     loadB(b0, 0, 0);
@@ -232,12 +243,54 @@ __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restric
     // ---- epilogue: gain / demodulation, strided store of each phase.  Block-uniform 64-bit base per phase, 32-bit lane offsets
     // (the first version formed a 64-bit address per element: ~2000 vector instructions per wave behind the last MFMA) -------------
     const int n = n0 + nq * 32 + li;
-    if (n >= p.Cout) return;
-    const float os = out_scale ? out_scale[(int64_t)pb * p.Cout + n] : 1.f;
     const unsigned rowstep = (unsigned)(2 * p.YW) * (unsigned)p.Cout;           // one position row = two output rows
     const unsigned colstep = 2u * (unsigned)p.Cout;
-    const unsigned lane_off = (unsigned)(4 * lh) * colstep + (unsigned)(nq * 32 + li);
     const bool full = qy0 + PH <= a.oh[3] && qx0 + PW <= a.ow[3];                 // block-uniform: nothing of the patch is masked
+    if constexpr (ST16) {
+        // 16 bytes per lane (Cout % 4 == 0, y 16-byte aligned).  An accumulator register holds ONE channel of a lane's position, so a
+        // store instruction of the form below covers two 128-byte lines with 64 dwords: 128 store instructions per wave, and the tail
+        // is bound by their issue, not by bandwidth.  The LDS buffers are dead behind the last chunk's barrier: per phase a wave
+        // writes its 64 positions x 32 channels (8 KB of its own: no block barrier; LDS operations of one wave complete in order)
+        // with the gain and out_scale applied as below, and reads them back with a lane holding 4 consecutive channels of one
+        // position: 32 store instructions per wave, each covering eight 128-byte lines.  Same mul_rn order: bitwise the same output.
+        // Slot of position q: q ^ ((q >> 2) & 1) -- the two half-waves (positions 4 apart = 512 B) then write different banks.
+        const float os = (out_scale && n < p.Cout) ? out_scale[(int64_t)pb * p.Cout + n] : 1.f;
+        static_assert(sizeof(smem) >= 4 * 64 * 32 * sizeof(float), "a wave's 8 KB of the epilogue must lie inside the allocation");
+        float* wl = reinterpret_cast<float*>(smem) + wave * (64 * 32);
+        const int cq = lane & 7, pg = lane >> 3;                                  // channel quad of the wave's 32, slot within a group of 8
+        const bool gok = n0 + nq * 32 + cq * 4 < p.Cout;                          // (Cout % 4 == 0: a quad is inside or outside as a whole)
+        const unsigned lane_off4 = (unsigned)(nq * 32 + cq * 4);
+#pragma unroll
+        for (int ph = 0; ph < 4; ++ph) {
+            float* yb = y + (((int64_t)pb * p.YH + 2 * qy0 + a.ooy[ph]) * p.YW + 2 * qx0 + a.oox[ph]) * p.Cout + n0;
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int q = aa * 32 + 8 * (e >> 2) + (e & 3);               // + 4 lh
+                    float v = mul_rn(acc[ph][aa][e], p.gain);
+                    if (out_scale) v = mul_rn(v, os);
+                    wl[((q + 4 * lh) ^ lh) * 32 + li] = v;
+                }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int slot = k * 8 + pg, q = slot ^ ((slot >> 2) & 1);
+                const int ry = q >> 4, cx = q & 15;
+                const float4 v = *reinterpret_cast<const float4*>(wl + k * 256 + lane * 4);
+                if (!gok || (!full && (qy0 + ry >= a.oh[ph] || qx0 + cx >= a.ow[ph]))) continue;
+                *reinterpret_cast<float4*>(yb + (lane_off4 + (unsigned)ry * rowstep + (unsigned)cx * colstep)) = v;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");               // the next phase overwrites what was just read
+            __builtin_amdgcn_wave_barrier();
+        }
+        return;
+    }
+    if (n >= p.Cout) return;
+    const float os = out_scale ? out_scale[(int64_t)pb * p.Cout + n] : 1.f;
+    const unsigned lane_off = (unsigned)(4 * lh) * colstep + (unsigned)(nq * 32 + li);
 #pragma unroll
     for (int ph = 0; ph < 4; ++ph) {
         float* yb = y + (((int64_t)pb * p.YH + 2 * qy0 + a.ooy[ph]) * p.YW + 2 * qx0 + a.oox[ph]) * p.Cout + n0;
@@ -279,6 +332,15 @@ static bool tphase_match(int n, const ideas_conv_params* ps, int (&order)[4]) {
     return (int64_t)p.B * p.IH * p.IW * p.Cin * 4 < 0xffffffffLL && (int64_t)4 * p.Cin * p.Cout * 6 < 0xffffffffLL;
 }
 
+// 16-byte stores of the epilogue where the output allows them; IDEAS_B3_TPHASE_STORE=0 (read per call) keeps the one-dword stores
+static bool tphase_store16(const void* y, int Cout) {
+    const char* es = getenv("IDEAS_B3_TPHASE_STORE");
+    return !(es && es[0] == '0') && Cout % 4 == 0 && ideas_aligned16(y);
+}
+// (for tests and A/B scripts: 1 when a launch of conv_b3_tphase_kernel writing Cout channels at y takes the 16-byte stores under the
+// present environment; a diagnostic that is not part of the ABI of include/ideas_hip.h and not bound by ideas_amd/_lib.py)
+extern "C" int ideas_b3_tphase_store16(const void* y, int Cout) { return tphase_store16(y, Cout) ? 1 : 0; }
+
 // called by ideas_b3_fwd_multi; returns -1 when the launches are not the canonical transposed-conv phases (IDEAS_B3_TPHASE=0: never).
 // The input grid of the phases has IH + 1 rows and IW + 1 columns, which no power-of-two patch divides (129 x 129 positions in 4 x 16
 // patches: 12 % of the blocks' positions idle).  When IH % 4 == 0 and IW % 16 == 0 the kernel therefore covers the IH x IW positions
@@ -310,12 +372,15 @@ int ideas_b3_fwd_tphase(int n, void* y, const void* x, const void* const* wplane
     const int tn = (p.Cout + 127) / 128;
     if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
     const unsigned x_bytes = (unsigned)((int64_t)p.B * p.IH * p.IW * p.Cin * 4);
-    if (in_scale)
-        hipLaunchKernelGGL(conv_b3_tphase_kernel<true>, dim3((unsigned)(tm * tn)), dim3(256), 0, stream, (float*)y, (const float*)x,
-                           in_scale, out_scale, p, a, QH, QW, tn, x_bytes);
-    else
-        hipLaunchKernelGGL(conv_b3_tphase_kernel<false>, dim3((unsigned)(tm * tn)), dim3(256), 0, stream, (float*)y, (const float*)x,
-                           in_scale, out_scale, p, a, QH, QW, tn, x_bytes);
+    const bool st16 = tphase_store16(y, p.Cout);
+    auto go = [&](auto sc, auto s16) {
+        hipLaunchKernelGGL((conv_b3_tphase_kernel<decltype(sc)::value, decltype(s16)::value>), dim3((unsigned)(tm * tn)), dim3(256), 0, stream,
+                           (float*)y, (const float*)x, in_scale, out_scale, p, a, QH, QW, tn, x_bytes);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    if (in_scale) { if (st16) go(T{}, T{}); else go(T{}, F{}); }
+    else { if (st16) go(F{}, T{}); else go(F{}, F{}); }
     if (exact) {
         // position row IH: phases (2x2) and (2x1) [output row 2 IH, even / odd columns]; position column IW, rows < IH: phases (2x2), (1x2)
         const int rowph[2] = {0, 1}, colph[2] = {0, 2};

@@ -18,6 +18,9 @@
 // wave-uniform.  Padding taps use the out-of-range buffer offset (hardware zero fill); rows past Cout / columns past
 // K compute on whatever the loads return and are not stored.  Requires OW % 4 == 0 (a 4-pixel group never straddles
 // an image row), 16 | OW or OW | 16, and B*OH*OW % 16 == 0 -- true for every layer of the networks.
+// (census with this file's packed f32 staging ops split into single instructions: no gain beyond the run-to-run spread,
+//  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
+#define B3_UNPACK_F32 0
 #include "b3.hpp"
 #include <type_traits>
 
@@ -125,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_wgrad_kernel(float* __restrict
         for (int c = 0; c < 4; ++c) {                // channel c of the quad: its 4 pixels -> one 8-byte group per plane
             float e[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) e[j] = SCALE ? mul_rn(vv[j][c], sc[c]) : vv[j][c];
+            for (int j = 0; j < 4; ++j) e[j] = SCALE ? b3_mul(vv[j][c], sc[c]) : vv[j][c];
             uint2 pl[3];
             split2(e[0], e[1], pl[0].x, pl[1].x, pl[2].x);
             split2(e[2], e[3], pl[0].y, pl[1].y, pl[2].y);

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_wgrad3_kernel(float* __restric
         }
     };
     auto put = [&](unsigned char* plane0, int plane_bytes, int row, float4 v, float4 sc) {
-        if (SCALE) v = make_float4(mul_rn(v.x, sc.x), mul_rn(v.y, sc.y), mul_rn(v.z, sc.z), mul_rn(v.w, sc.w));
+        if (SCALE) v = b3_scale4(v, sc);
         const Split4 s = split4(v);
         unsigned char* a = plane0 + chunk_off(row, quad >> 1) + (quad & 1) * 8;
 #pragma unroll

@@ -20,6 +20,9 @@
 // LDS: two pipeline buffers of the 12 A planes (2 x 24 KB), one barrier per step.
 // Epilogue: the four components of an output pair live in four different waves; they meet in LDS (two 32-channel halves),
 // then out = inverse transform -> gain / demod / bias / act / residual exactly as conv_wino.hip.
+// (census with this file's packed f32 staging ops split into single instructions: no gain beyond the run-to-run spread,
+//  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
+#define B3_UNPACK_F32 0
 #include "b3.hpp"
 #ifndef WINO_ABL
 #define WINO_ABL 0
@@ -327,7 +330,7 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 3 : 1) void conv_b3_wino_kernel
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float4 e = v[c];
-            if (SCALE) e = make_float4(mul_rn(e.x, st.s.x), mul_rn(e.y, st.s.y), mul_rn(e.z, st.s.z), mul_rn(e.w, st.s.w));
+            if (SCALE) e = b3_scale4(e, st.s);
             const Split4 s = split4(e);
 #pragma unroll
             for (int q = 0; q < 3; ++q) pl.q[c][q] = s.p[q];
@@ -627,7 +630,7 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float4 e = v[c];
-            if (SCALE) e = make_float4(mul_rn(e.x, st.s.x), mul_rn(e.y, st.s.y), mul_rn(e.z, st.s.z), mul_rn(e.w, st.s.w));
+            if (SCALE) e = b3_scale4(e, st.s);
             const Split4 s = split4(e);
 #pragma unroll
             for (int q = 0; q < 3; ++q) pl.q[c][q] = s.p[q];

@@ -1,11 +1,17 @@
 // upfirdn2d for gfx950: zero-stuff / pad / FIR (flipped) / decimate.
 //
-// Replaces upfirdn2d_kernel + upfirdn2d_kernel_large (stylegan2/op/upfirdn2d_kernel.cu:49-207).  On the IDEAS
-// path this op is only ever a 4x4 blur with up = down = 1, pure HBM traffic: read the plane
-// once, write it once.  Three kernels:
-//   * blur4_nhwc  — the fast path.  Channels are innermost, so a thread owns 4 channels of one output
-//                   column and marches down the rows with a 4x4 register window: 4 x 16-byte loads and one
-//                   16-byte store per output, every access coalesced along C, no LDS needed.
+// Replaces upfirdn2d_kernel + upfirdn2d_kernel_large (stylegan2/op/upfirdn2d_kernel.cu:49-207).  On the IDEAS path this op is a 4x4
+// FIR on channels-last tensors -- the blur (up = down = 1), the decimating FIR in front of a stride-2 skip conv and its adjoint,
+// the zero-stuffing FIR -- and pure HBM traffic: read the plane once, write it once.  The kernels:
+//   * the 4x4 NHWC schemes, one body each, instantiated over the storage vector (f32 x 4, bf16 x 4, bf16 / f16 x 8) and built from
+//     one set of shared pieces: tap staging, factorisation, thread-to-tile decode, fused stage, and a row loader with TWO border
+//     policies (clamped + masked loads for the raw 16-byte rows; skipped loads for the 4-channel float windows, load_row_f):
+//       blur4_c2           the blur, two output columns per thread, separable window (blur4_bf16x8_c2): the fast path;
+//       blur4_f32_c2       the same scheme in its own float4 form (the merged body measured slower in f32, see there)
+//       blur4_nhwc         the blur, one column per thread, direct 4x4 window (bf16 at C % 8 == 4)
+//       fir4_down2_nhwc    down = 2, direct window, 4 channels per thread
+//       fir4_down2_bf16x8  down = 2, separable window, 8 channels per thread
+//       fir4_up2           up = 2 (+ residual)
 //   * blur_nchw_tile — NCHW (the reference's layout): LDS-staged (TH+kh-1) x (TW+kw-1) input tile per plane.
 //   * generic     — any up/down/FIR size, either layout, any dtype, one output per thread (the op's full contract).
 #include "common.hpp"
@@ -17,7 +23,7 @@ struct FirParams {
     int up_x, up_y, down_x, down_y, pad_x0, pad_y0;
     float gain;
     int flip;
-    int seg_rows;   // blur4_nhwc: output rows marched per thread
+    int seg_rows;   // the 4x4 NHWC kernels: rows (block rows for up = 2) marched per thread
 };
 
 // ---------------- generic: out[oy,ox] = sum_k U[oy*down + ky - pad0] * Kf[ky] ----------------------
@@ -75,8 +81,10 @@ __global__ __launch_bounds__(256) void upfirdn2d_generic(T* __restrict__ y, cons
     }
 }
 
-// ---------------- NHWC 4x4 blur, up = down = 1 ---------------------------------------------------
-// thread = (b, row-segment, ox, c4); window w[r][t] holds input rows iy0..iy0+3 at columns ix0..ix0+3
+// ---------------- the 4x4 NHWC kernels: shared pieces ----------------------------------------------------------------------------
+// A thread owns one channel vector (4 or 8 channels) of one output column, column pair or 2 x 2 block and marches down a segment of
+// rows with its window in registers.  The schemes below differ in the window; taps, decode, loader and fused stage are these.
+//
 // EPI: a fused elementwise stage on the blurred value before it is stored (ideas_blur_fused):
 //   EPI_ACT_BWD   y = (ref > 0 ? v : v * alpha) * scale, bias_grad[c] += sum y    -- blur^T followed by the leaky-ReLU backward
 //                                                                                   of the layer below (ref = its saved output)
@@ -104,299 +112,19 @@ __device__ __forceinline__ void bgrad_flush(float* s_bg, float* __restrict__ bgr
     }
 }
 
-template <typename V, int EPI>
-__global__ __launch_bounds__(256) void blur4_nhwc(V* __restrict__ y, const V* __restrict__ x,
-                                                  const float* __restrict__ fir, FirParams p, FirEpi ep) {
-    __shared__ float sk[16];
-    extern __shared__ float s_bg[];
-    if (threadIdx.x < 16) {
-        int t = threadIdx.x;
-        int src = p.flip ? 15 - t : t;
-        sk[t] = fir[src] * p.gain;
-    }
-    __syncthreads();
-    const int C4 = p.C >> 2;
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * p.out_w * C4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < total;
-    if (EPI != EPI_ACT_BWD && !active) return;
-    // EPI_ACT_BWD ends in block barriers (bgrad_flush), which every lane of every wave has to reach along the SAME path: threads
-    // past the end redo the last thread's work with their stores and their share of the bias gradient masked off
-    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    int64_t r = active ? i : total - 1;
-    const int c4 = (int)(r % C4); r /= C4;
-    const int ox = (int)(r % p.out_w); r /= p.out_w;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
-    const int ix0 = ox - p.pad_x0;
-    float k[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) k[t] = sk[t];
-
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const V* xb = x + (int64_t)b * p.in_h * p.in_w * C4 + c4;
-    unsigned colmask = 0;   // bit t: column ix0+t is inside the image (a bool[4] ends up in scratch memory)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
-
-    float4 w[4][4];
-    auto load_row = [&](int iy, float4 (&dst)[4]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const V* xr = xb + ((int64_t)iy * p.in_w + ix0) * C4;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            float4 v = zero;
-            if (rowok && ((colmask >> t) & 1u)) v = to_f4(xr[(int64_t)t * C4]);
-            dst[t] = v;
-        }
-    };
-    const int iy0 = oy0 - p.pad_y0;
-    load_row(iy0 + 0, w[0]);
-    load_row(iy0 + 1, w[1]);
-    load_row(iy0 + 2, w[2]);
-    V* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C4 + c4;
-    const V* rb = reinterpret_cast<const V*>(ep.ref) + (((int64_t)b * p.out_h) * p.out_w + ox) * C4 + c4;
-    float4 bb = zero;
-    if (EPI == EPI_BIAS_ACT) bb = *reinterpret_cast<const float4*>(ep.bias + 4 * c4);
-    auto emit = [&](int oy, const float4 (&r0)[4], const float4 (&r1)[4], const float4 (&r2)[4], const float4 (&r3)[4]) {
-        float4 acc = zero;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float k0 = k[t], k1 = k[4 + t], k2 = k[8 + t], k3 = k[12 + t];
-            acc.x += r0[t].x * k0 + r1[t].x * k1 + r2[t].x * k2 + r3[t].x * k3;
-            acc.y += r0[t].y * k0 + r1[t].y * k1 + r2[t].y * k2 + r3[t].y * k3;
-            acc.z += r0[t].z * k0 + r1[t].z * k1 + r2[t].z * k2 + r3[t].z * k3;
-            acc.w += r0[t].w * k0 + r1[t].w * k1 + r2[t].w * k2 + r3[t].w * k3;
-        }
-        if (EPI == EPI_ACT_BWD) {
-            const float4 rf = to_f4(rb[(int64_t)oy * p.out_w * C4]);
-            if (sizeof(V) != sizeof(float4)) acc = to_f4(from_f4<V>(acc));       // bf16: the unfused path stores the blur first
-            acc = make_float4(epi_act(acc.x, rf.x, ep.alpha, ep.scale), epi_act(acc.y, rf.y, ep.alpha, ep.scale),
-                              epi_act(acc.z, rf.z, ep.alpha, ep.scale), epi_act(acc.w, rf.w, ep.alpha, ep.scale));
-            bsum.x += acc.x; bsum.y += acc.y; bsum.z += acc.z; bsum.w += acc.w;
-            if (!active) return;
-        }
-        if (EPI == EPI_BIAS_ACT) {
-            if (sizeof(V) != sizeof(float4)) acc = to_f4(from_f4<V>(acc));
-            const float4 v = make_float4(acc.x + bb.x, acc.y + bb.y, acc.z + bb.z, acc.w + bb.w);
-            acc = make_float4(epi_act(v.x, v.x, ep.alpha, ep.scale), epi_act(v.y, v.y, ep.alpha, ep.scale),
-                              epi_act(v.z, v.z, ep.alpha, ep.scale), epi_act(v.w, v.w, ep.alpha, ep.scale));
-        }
-        yb[(int64_t)oy * p.out_w * C4] = from_f4<V>(acc);
-    };
-    // two output rows per trip: 8 independent 16-byte loads in flight instead of 4 (the window shift is a
-    // dependent chain, so one row per trip is latency-bound)
-    float4 w4[4];
-    int oy = oy0;
-    for (; oy + 1 < oy1; oy += 2) {
-        load_row(oy - p.pad_y0 + 3, w[3]);
-        load_row(oy - p.pad_y0 + 4, w4);
-        emit(oy, w[0], w[1], w[2], w[3]);
-        emit(oy + 1, w[1], w[2], w[3], w4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { w[0][t] = w[2][t]; w[1][t] = w[3][t]; w[2][t] = w4[t]; }
-    }
-    if (oy < oy1) {
-        load_row(oy - p.pad_y0 + 3, w[3]);
-        emit(oy, w[0], w[1], w[2], w[3]);
-    }
-    if (EPI == EPI_ACT_BWD) {
-        const float part[4] = {bsum.x, bsum.y, bsum.z, bsum.w};
-        bgrad_flush(s_bg, ep.bgrad, p.C, active, 4 * c4, part, 4);
-    }
-}
-
-// ---------------- NHWC 4x4 FIR with decimation by 2 (up = 1, down = 2) ----------------------------------------------------
-// The blur in front of a 1x1 stride-2 skip conv only feeds every second pixel of every second row into the conv
-// (models.py:78-95): computing it at the OUTPUT resolution writes N/4 instead of N and lets the conv run unstrided.
-// Same marching scheme as blur4_nhwc, the window advances two input rows per output row (8 loads, 1 store per output).
-template <typename V>
-__global__ __launch_bounds__(256) void fir4_down2_nhwc(V* __restrict__ y, const V* __restrict__ x, const float* __restrict__ fir,
-                                                       FirParams p) {
-    __shared__ float sk[16];
+// the 16 flipped, gain-scaled taps -> LDS
+__device__ __forceinline__ void stage_taps(float (&sk)[16], const float* __restrict__ fir, const FirParams& p) {
     if (threadIdx.x < 16) {
         const int t = threadIdx.x;
         sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
     }
     __syncthreads();
-    const int C4 = p.C >> 2;
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * p.out_w * C4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int64_t r = i;
-    const int c4 = (int)(r % C4); r /= C4;
-    const int ox = (int)(r % p.out_w); r /= p.out_w;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
-    const int ix0 = 2 * ox - p.pad_x0;
-    float k[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) k[t] = sk[t];
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const V* xb = x + (int64_t)b * p.in_h * p.in_w * C4 + c4;
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
-    auto load_row = [&](int iy, float4 (&dst)[4]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const V* xr = xb + ((int64_t)iy * p.in_w + ix0) * C4;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            float4 v = zero;
-            if (rowok && ((colmask >> t) & 1u)) v = to_f4(xr[(int64_t)t * C4]);
-            dst[t] = v;
-        }
-    };
-    float4 w[4][4];
-    load_row(2 * oy0 - p.pad_y0 + 0, w[0]);
-    load_row(2 * oy0 - p.pad_y0 + 1, w[1]);
-    V* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C4 + c4;
-    for (int oy = oy0; oy < oy1; ++oy) {
-        load_row(2 * oy - p.pad_y0 + 2, w[2]);
-        load_row(2 * oy - p.pad_y0 + 3, w[3]);
-        float4 acc = zero;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float kk = k[4 * j + t];
-                acc.x = fmaf(w[j][t].x, kk, acc.x); acc.y = fmaf(w[j][t].y, kk, acc.y);
-                acc.z = fmaf(w[j][t].z, kk, acc.z); acc.w = fmaf(w[j][t].w, kk, acc.w);
-            }
-        yb[(int64_t)oy * p.out_w * C4] = from_f4<V>(acc);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { w[0][t] = w[2][t]; w[1][t] = w[3][t]; }
-    }
 }
 
-// ---------------- NHWC 4x4 FIR after zero-stuffing by 2 (up = 2, down = 1) ---------------------------------------------
-// The adjoint of the kernel above (its backward), and the blur behind a 1x1 stride-2 TRANSPOSED skip conv (three of four
-// pixels of that conv's output are structural zeros; here they are never written or read).  Per axis, output o = 2i + a
-// (a = 0, 1) sees the two taps k = k0(a), k0(a) + 2 with k0(a) = (pad0 - a) & 1, at inputs i + d(a), i + d(a) + 1,
-// d(a) = (a + k0(a) - pad0) / 2 -- so a 2 x 2 output block needs a 3 x 3 input neighbourhood.  A thread owns the output
-// column pair (2j, 2j + 1) of 4 channels and marches down block rows: 3 loads and 4 stores per block row.
-// `resid` (optional, same shape as y): y = fir(x) + resid -- the residual merge behind an upsampling skip, and (as the adjoint of
-// fir4_down2) the sum of the two input gradients of a downsampling ResBlock, without a separate add pass (ideas_fir_up2_add).
-template <typename V>
-__global__ __launch_bounds__(256) void fir4_up2_nhwc(V* __restrict__ y, const V* __restrict__ x, const float* __restrict__ fir,
-                                                     FirParams p, const V* __restrict__ resid) {
-    __shared__ float sk[16];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
-    const int C4 = p.C >> 2;
-    const int bh = (p.out_h + 1) >> 1, bw = (p.out_w + 1) >> 1;          // 2 x 2 output blocks
-    const int segs = (bh + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * bw * C4;
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    int64_t r = idx;
-    const int c4 = (int)(r % C4); r /= C4;
-    const int j = (int)(r % bw); r /= bw;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int i0 = seg * p.seg_rows;
-    const int i1 = (i0 + p.seg_rows < bh) ? i0 + p.seg_rows : bh;
-    // per-axis tap / offset tables (a = output parity)
-    const int ky0[2] = {p.pad_y0 & 1, (p.pad_y0 - 1) & 1}, kx0[2] = {p.pad_x0 & 1, (p.pad_x0 - 1) & 1};
-    const int dy[2] = {(ky0[0] - p.pad_y0) >> 1, (1 + ky0[1] - p.pad_y0) >> 1};
-    const int dx[2] = {(kx0[0] - p.pad_x0) >> 1, (1 + kx0[1] - p.pad_x0) >> 1};
-    const int ey = dy[1] - dy[0], ex = dx[1] - dx[0];                       // 0 or 1: which 2 of the 3 rows / columns parity 1 uses
-    float wq[2][2][2][2];                                                  // [a][bb][u][v]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int v = 0; v < 2; ++v) wq[a][bb][u][v] = sk[(ky0[a] + 2 * u) * 4 + kx0[bb] + 2 * v];
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const V* xb = x + (int64_t)b * p.in_h * p.in_w * C4 + c4;
-    const int cx0 = j + dx[0];
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) colmask |= ((cx0 + t >= 0) && (cx0 + t < p.in_w)) ? (1u << t) : 0u;
-    auto load_row = [&](int iy, float4 (&dst)[3]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const V* xr = xb + ((int64_t)iy * p.in_w + cx0) * C4;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            float4 v = zero;
-            if (rowok && ((colmask >> t) & 1u)) v = to_f4(xr[(int64_t)t * C4]);
-            dst[t] = v;
-        }
-    };
-    float4 R[3][3];
-    load_row(i0 + dy[0] + 0, R[0]);
-    load_row(i0 + dy[0] + 1, R[1]);
-    const bool colB = 2 * j + 1 < p.out_w;
-    for (int i = i0; i < i1; ++i) {
-        load_row(i + dy[0] + 2, R[2]);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int oy = 2 * i + a;
-            if (oy >= p.out_h) break;
-            // rows of this parity: R[ra], R[ra + 1] with ra = a ? ey : 0 (selected without dynamic register indexing)
-            float4 top[3], bot[3];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const bool hi = (a == 1) && (ey == 1);
-                top[t] = hi ? R[1][t] : R[0][t];
-                bot[t] = hi ? R[2][t] : R[1][t];
-            }
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                if (bb == 1 && !colB) break;
-                const bool hx = (bb == 1) && (ex == 1);
-                const float4 t0 = hx ? top[1] : top[0], t1 = hx ? top[2] : top[1];
-                const float4 b0 = hx ? bot[1] : bot[0], b1 = hx ? bot[2] : bot[1];
-                const float w00 = wq[a][bb][0][0], w01 = wq[a][bb][0][1], w10 = wq[a][bb][1][0], w11 = wq[a][bb][1][1];
-                float4 acc;
-                acc.x = t0.x * w00 + t1.x * w01 + b0.x * w10 + b1.x * w11;
-                acc.y = t0.y * w00 + t1.y * w01 + b0.y * w10 + b1.y * w11;
-                acc.z = t0.z * w00 + t1.z * w01 + b0.z * w10 + b1.z * w11;
-                acc.w = t0.w * w00 + t1.w * w01 + b0.w * w10 + b1.w * w11;
-                const int64_t yi = (((int64_t)b * p.out_h + oy) * p.out_w + 2 * j + bb) * C4 + c4;
-                if (resid) {
-                    if (sizeof(V) != sizeof(float4)) acc = to_f4(from_f4<V>(acc));     // bf16: the two-kernel chain stores the FIR first
-                    const float4 rv = to_f4(resid[yi]);
-                    acc = make_float4(acc.x + rv.x, acc.y + rv.y, acc.z + rv.z, acc.w + rv.w);
-                }
-                y[yi] = from_f4<V>(acc);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 3; ++t) { R[0][t] = R[1][t]; R[1][t] = R[2][t]; }
-    }
-}
-
-// ---------------- f32 NHWC 4x4 blur, two output columns per thread (separable FIR) ---------------------------------------------
-// blur4_nhwc issues four 16-byte loads per 16-byte output and is bound by load instructions, not by HBM (4.5-5.0 TB/s against the
-// 5.5-6 of a plain streaming kernel).  A thread that owns the column pair (2q, 2q+1) loads five vectors per row for two outputs and
-// -- every FIR of the path being an outer product kv (x) kh (make_kernel, stylegan2/model.py:22-30) -- keeps two horizontally
-// filtered values per row instead of a 4 x 5 window.  The factorisation is checked on the device; a rank > 1 table takes a direct
-// loop.  (Summation order differs from blur4_nhwc in the last bit; fused and unfused stages share this kernel, so they still agree
-// bitwise with each other.)
-template <int EPI>
-__global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, const float4* __restrict__ x,
-                                                    const float* __restrict__ fir, FirParams p, FirEpi ep) {
-    __shared__ float sk[16];
-    extern __shared__ float s_bg[];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
-    float kh[4], kv[4];
+// Every FIR of the path is an outer product kv (x) kh (make_kernel, stylegan2/model.py:22-30).  The factorisation is checked on the
+// device from the 16 taps: kh = first row, kv = first column / its first element; false (block-uniform) for a rank > 1 table, which
+// takes a scheme's direct 16-tap loop.
+__device__ __forceinline__ bool factor_taps(const float (&sk)[16], float (&kh)[4], float (&kv)[4]) {
     float kmax = 0.f, res = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) { kh[t] = sk[t]; kv[t] = sk[0] != 0.f ? sk[4 * t] / sk[0] : 0.f; }
@@ -404,40 +132,284 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int t = 0; t < 4; ++t) { kmax = fmaxf(kmax, fabsf(sk[4 * j + t])); res = fmaxf(res, fabsf(sk[4 * j + t] - kv[j] * kh[t])); }
-    const bool sep = res <= 1e-6f * kmax;           // block-uniform
-    const int C4 = p.C >> 2;
-    const int pw = (p.out_w + 1) >> 1;
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * pw * C4;
+    return res <= 1e-6f * kmax;
+}
+
+// thread -> (channel vector cv, column col, row segment seg of batch element b: rows r0 .. r1 - 1) on a grid of `cols` columns (or
+// column pairs, or 2 x 2 blocks) and `rows` rows; false for the threads past the end.  EPI_ACT_BWD ends in block barriers
+// (bgrad_flush), which every lane of every wave has to reach along the SAME path: there the threads past the end redo the last
+// thread's work with their stores and their share of the bias gradient masked off, so they are given its tile.
+struct Tile { int cv, col, seg, b, r0, r1; };
+__device__ __forceinline__ bool decode_tile(Tile& t, const FirParams& p, int CV, int cols, int rows) {
+    const int segs = (rows + p.seg_rows - 1) / p.seg_rows;
+    const int64_t total = (int64_t)p.B * segs * cols * CV;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < total;
+    int64_t r = active ? i : total - 1;
+    t.cv = (int)(r % CV); r /= CV;
+    t.col = (int)(r % cols); r /= cols;
+    t.seg = (int)(r % segs);
+    t.b = (int)(r / segs);
+    t.r0 = t.seg * p.seg_rows;
+    t.r1 = (t.r0 + p.seg_rows < rows) ? t.r0 + p.seg_rows : rows;
+    return active;
+}
+
+// The three storage vectors as N = 1 << SHIFT floats: f32 x 4 (16 bytes), bf16 x 4 (8 bytes) and eight 2-byte elements E = ideas_bf16
+// or _Float16 (16 bytes); arithmetic is f32 for all (exact widening, RNE narrowing, see unpack8 / pack8).
+//   mask     the loaded vector, or zeros: component-wise (a ternary on the aggregate becomes a select between ADDRESSES and spills
+//            to scratch)
+//   round    through the storage type, as a kernel chain that stores the value in between rounds it (the identity for f32)
+__device__ __forceinline__ unsigned keep_bits(bool ok) { return ok ? 0xffffffffu : 0u; }
+struct VecF32 {
+    typedef float4 raw;
+    static constexpr int N = 4, SHIFT = 2;
+    static __device__ __forceinline__ raw mask(const raw& w, bool ok) { return make_float4(ok ? w.x : 0.f, ok ? w.y : 0.f, ok ? w.z : 0.f, ok ? w.w : 0.f); }
+    static __device__ __forceinline__ void unpack(const raw& w, float (&f)[4]) { f[0] = w.x; f[1] = w.y; f[2] = w.z; f[3] = w.w; }
+    static __device__ __forceinline__ raw pack(const float (&f)[4]) { return make_float4(f[0], f[1], f[2], f[3]); }
+    static __device__ __forceinline__ void round(float (&)[4]) {}
+};
+struct VecBf16x4 {
+    typedef ideas_bf16x4 raw;
+    static constexpr int N = 4, SHIFT = 2;
+    static __device__ __forceinline__ raw mask(const raw& w, bool ok) {
+        const unsigned m = keep_bits(ok);
+        raw r;
+        r.v = make_uint2(w.v.x & m, w.v.y & m);
+        return r;
+    }
+    static __device__ __forceinline__ void unpack(const raw& w, float (&f)[4]) { VecF32::unpack(to_f4(w), f); }
+    static __device__ __forceinline__ raw pack(const float (&f)[4]) { return from_f4<raw>(VecF32::pack(f)); }
+    static __device__ __forceinline__ void round(float (&f)[4]) { unpack(pack(f), f); }
+};
+template <typename E> struct VecX8 {
+    typedef uint4 raw;
+    static constexpr int N = 8, SHIFT = 3;
+    static __device__ __forceinline__ raw mask(const raw& w, bool ok) {
+        const unsigned m = keep_bits(ok);
+        return make_uint4(w.x & m, w.y & m, w.z & m, w.w & m);
+    }
+    static __device__ __forceinline__ void unpack(const raw& w, float (&f)[8]) { unpack8(w, f, E{}); }
+    static __device__ __forceinline__ raw pack(const float (&f)[8]) { return pack8(f, E{}); }
+    static __device__ __forceinline__ void round(float (&f)[8]) { unpack(pack(f), f); }
+};
+template <int N> struct Fv { float v[N]; };      // one vector's floats, as a value
+
+// r0 k0 + r1 k1 + r2 k2 + r3 k3 as fma(r0, k0, r1 k1) and then one fma per further term.  Written out: left to the compiler's
+// contraction, which of the first two products becomes the addend depends on the operand order the vectoriser leaves the sum in, and
+// results moved in the last bit with the code around the sum (conv_b3_s2fir.hip restates this order to agree bitwise with the blur).
+__device__ __forceinline__ float dot4(float r0, float r1, float r2, float r3, float k0, float k1, float k2, float k3) {
+    return fmaf(r3, k3, fmaf(r2, k2, fmaf(r0, k0, r1 * k1)));
+}
+
+// bit t: column ix0 + t is inside the image (a bool[NC] ends up in scratch memory)
+template <int NC> __device__ __forceinline__ unsigned col_mask(int ix0, int in_w) {
+    unsigned m = 0;
+#pragma unroll
+    for (int t = 0; t < NC; ++t) m |= ((ix0 + t >= 0) && (ix0 + t < in_w)) ? (1u << t) : 0u;
+    return m;
+}
+// columns ix0 .. ix0 + NC - 1 of input row iy (xb: the thread's batch element and channel vector), zeros outside the image.  Loads
+// are clamped + masked by value: the address is always a valid one, so NC independent loads are in flight whatever the borders are.
+template <typename T, int NC>
+__device__ __forceinline__ void load_row(typename T::raw (&dst)[NC], const typename T::raw* __restrict__ xb, int iy, int ix0, unsigned colmask,
+                                         const FirParams& p, int CV) {
+    const bool rowok = (iy >= 0) && (iy < p.in_h);
+    const typename T::raw* xr = xb + (int64_t)(rowok ? iy : 0) * p.in_w * CV;
+#pragma unroll
+    for (int t = 0; t < NC; ++t) {
+        const bool ok = rowok && ((colmask >> t) & 1u);
+        dst[t] = T::mask(xr[(int64_t)(ok ? ix0 + t : 0) * CV], ok);
+    }
+}
+// ... as floats.  A second border policy, for the 4-channel windows: they skip the loads outside the image (a branch per vector)
+// instead of clamping and masking them -- measured 3-6 % faster there, f32 at 4.4-5.2 TB/s, and the registers they always had.
+template <typename T, int NC>
+__device__ __forceinline__ void load_row_f(Fv<T::N> (&dst)[NC], const typename T::raw* __restrict__ xb, int iy, int ix0, unsigned colmask,
+                                           const FirParams& p, int CV) {
+    if constexpr (T::N == 4) {
+        const bool rowok = (iy >= 0) && (iy < p.in_h);
+        const typename T::raw* xr = xb + ((int64_t)iy * p.in_w + ix0) * CV;
+#pragma unroll
+        for (int t = 0; t < NC; ++t) {
+            dst[t] = Fv<T::N>{};
+            if (rowok && ((colmask >> t) & 1u)) T::unpack(xr[(int64_t)t * CV], dst[t].v);
+        }
+    } else {
+        typename T::raw v[NC];
+        load_row<T, NC>(v, xb, iy, ix0, colmask, p, CV);
+#pragma unroll
+        for (int t = 0; t < NC; ++t) T::unpack(v[t], dst[t].v);
+    }
+}
+
+// the fused stage of one output vector, then its store at yb[off].  The blur is rounded to the storage type first, as the unfused
+// blur -> bias_act chain stores it.  rb: ep.ref at yb's position; bb: the thread's biases; bsum: its partial bias gradient.
+template <typename T, int EPI>
+__device__ __forceinline__ void finish(typename T::raw* __restrict__ yb, const typename T::raw* __restrict__ rb, int64_t off, float (&o)[T::N],
+                                       const float (&bb)[T::N], float (&bsum)[T::N], const FirEpi& ep, bool active) {
+    if (EPI != EPI_NONE) T::round(o);
+    if (EPI == EPI_ACT_BWD) {
+        float rf[T::N];
+        T::unpack(rb[off], rf);
+#pragma unroll
+        for (int e = 0; e < T::N; ++e) { o[e] = epi_act(o[e], rf[e], ep.alpha, ep.scale); bsum[e] += o[e]; }
+        if (!active) return;
+    }
+    if (EPI == EPI_BIAS_ACT) {
+#pragma unroll
+        for (int e = 0; e < T::N; ++e) { const float v = o[e] + bb[e]; o[e] = epi_act(v, v, ep.alpha, ep.scale); }
+    }
+    yb[off] = T::pack(o);
+}
+
+// ---------------- 4x4 blur, up = down = 1, TWO output columns per thread (separable FIR) ------------------------------------------
+// A 4x4 window per output issues four loads per output vector and is bound by load instructions, not by HBM (f32: 4.5-5.0 TB/s against
+// the 5.5-6 of a plain streaming kernel; bf16 with 8-byte lanes: 1.45 TB/s).  A thread that owns the column pair (2q, 2q+1) loads five
+// vectors per row for two outputs (the windows overlap in three columns) and -- the FIR being an outer product, factor_taps -- keeps
+// two horizontally filtered values per row instead of a 4 x 5 window: each input row is reduced as it arrives, and the window is
+// four of those per column.  A rank > 1 table takes a direct loop.  (Summation order differs from blur4_nhwc in the last bit; fused
+// and unfused stages share this body, so they still agree bitwise with each other.)
+template <typename T, int EPI>
+__device__ __forceinline__ void blur4_c2(typename T::raw* __restrict__ y, const typename T::raw* __restrict__ x, const float* __restrict__ fir,
+                                         const FirParams& p, const FirEpi& ep, float (&sk)[16], float* s_bg) {
+    typedef typename T::raw raw;
+    constexpr int N = T::N;
+    stage_taps(sk, fir, p);
+    float kh[4], kv[4];
+    const bool sep = factor_taps(sk, kh, kv);
+    const int CV = p.C >> T::SHIFT;
+    Tile tl;
+    const bool active = decode_tile(tl, p, CV, (p.out_w + 1) >> 1, p.out_h);
     if (EPI != EPI_ACT_BWD && !active) return;
-    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    int64_t r = active ? i : total - 1;      // (see blur4_nhwc: one path to the barriers of bgrad_flush)
-    const int c4 = (int)(r % C4); r /= C4;
-    const int q = (int)(r % pw); r /= pw;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int ox = 2 * q;
+    const int ox = 2 * tl.col;
     const bool colB = ox + 1 < p.out_w;
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
+    const int oy0 = tl.r0, oy1 = tl.r1;
+    const int ix0 = ox - p.pad_x0;
+    const raw* xb = x + (int64_t)tl.b * p.in_h * p.in_w * CV + tl.cv;
+    raw* yb = y + (((int64_t)tl.b * p.out_h) * p.out_w + ox) * CV + tl.cv;
+    const raw* rb = reinterpret_cast<const raw*>(ep.ref) + (((int64_t)tl.b * p.out_h) * p.out_w + ox) * CV + tl.cv;
+    float bb[N] = {}, bsum[N] = {};
+    if (EPI == EPI_BIAS_ACT) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) bb[e] = ep.bias[N * tl.cv + e];
+    }
+    auto fin = [&](int oy, int col, float (&o)[N]) {
+        finish<T, EPI>(yb, rb, (int64_t)oy * p.out_w * CV + (int64_t)col * CV, o, bb, bsum, ep, active);
+    };
+    const unsigned colmask = col_mask<5>(ix0, p.in_w);
+    if (!sep) {      // direct 16-tap form, one output at a time: correct for any FIR, not tuned
+#pragma unroll 1
+        for (int oy = oy0; oy < oy1; ++oy)
+#pragma unroll 1
+            for (int col = 0; col < (colB ? 2 : 1); ++col) {
+                float acc[N] = {};
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                    const int iy = oy - p.pad_y0 + j;
+                    if (iy < 0 || iy >= p.in_h) continue;
+#pragma unroll 1
+                    for (int t = 0; t < 4; ++t) {
+                        const int ix = ix0 + col + t;
+                        if (ix < 0 || ix >= p.in_w) continue;
+                        float f[N];
+                        T::unpack(xb[((int64_t)iy * p.in_w + ix) * CV], f);
+#pragma unroll
+                        for (int e = 0; e < N; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
+                    }
+                }
+                fin(oy, col, acc);
+            }
+        if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, N * tl.cv, bsum, N);
+        return;
+    }
+    // one input row -> its two horizontally filtered values (columns ox and ox + 1)
+    auto hrow = [&](int iy, Fv<N>& ha, Fv<N>& hb) {
+        raw v[5];
+        load_row<T, 5>(v, xb, iy, ix0, colmask, p, CV);
+#pragma unroll
+        for (int e = 0; e < N; ++e) { ha.v[e] = 0.f; hb.v[e] = 0.f; }
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            float f[N];
+            T::unpack(v[t], f);
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                if (t < 4) ha.v[e] = fmaf(f[e], kh[t], ha.v[e]);
+                if (t > 0) hb.v[e] = fmaf(f[e], kh[t - 1], hb.v[e]);
+            }
+        }
+    };
+    auto emit = [&](int oy, const Fv<N>& a0, const Fv<N>& a1, const Fv<N>& a2, const Fv<N>& a3, const Fv<N>& b0, const Fv<N>& b1, const Fv<N>& b2,
+                    const Fv<N>& b3) {
+        float o[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) o[e] = dot4(a0.v[e], a1.v[e], a2.v[e], a3.v[e], kv[0], kv[1], kv[2], kv[3]);
+        fin(oy, 0, o);
+        if (colB) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) o[e] = dot4(b0.v[e], b1.v[e], b2.v[e], b3.v[e], kv[0], kv[1], kv[2], kv[3]);
+            fin(oy, 1, o);
+        }
+    };
+    Fv<N> a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
+    {
+        const int iy0 = oy0 - p.pad_y0;
+        hrow(iy0 + 0, a0, b0); hrow(iy0 + 1, a1, b1); hrow(iy0 + 2, a2, b2);
+    }
+    int oy = oy0;
+#pragma unroll 1
+    for (; oy + 1 < oy1; oy += 2) {      // two output rows per trip: ten loads in flight (the window shift is a dependent chain)
+        hrow(oy - p.pad_y0 + 3, a3, b3);
+        hrow(oy - p.pad_y0 + 4, a4, b4);
+        emit(oy, a0, a1, a2, a3, b0, b1, b2, b3);
+        emit(oy + 1, a1, a2, a3, a4, b1, b2, b3, b4);
+        a0 = a2; a1 = a3; a2 = a4; b0 = b2; b1 = b3; b2 = b4;
+    }
+    if (oy < oy1) {
+        hrow(oy - p.pad_y0 + 3, a3, b3);
+        emit(oy, a0, a1, a2, a3, b0, b1, b2, b3);
+    }
+    if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, N * tl.cv, bsum, N);
+}
+// (blur4_f32_c2 and blur4_bf16x8_c2: the names bench.py and tools/summarize_profiles.py find these kernels by in a profile)
+// The f32 instantiation keeps its own float4 form of that body (the tap, decode and column-mask pieces are the shared ones): as
+// blur4_c2<VecF32> the same arithmetic compiled to 82-99 VGPRs against 132 with another load schedule and measured 2-9 % below
+// this form on the 128- and 256-pixel shapes, with or without an occupancy hint; this form compiles to the registers and the
+// instruction mix it always had (132 / 122 / 98 VGPRs for EPI 0 / 1 / 2).  Its vertical sum r0 kv0 + r1 kv1 + r2 kv2 + r3 kv3 is left to
+// the compiler's contraction, which here gives dot4's order (tests/test_fir_pinned_gpu.py holds both forms to the same bytes).
+template <int EPI>
+__global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, const float4* __restrict__ x,
+                                                    const float* __restrict__ fir, FirParams p, FirEpi ep) {
+    __shared__ float sk[16];
+    extern __shared__ float s_bg[];
+    stage_taps(sk, fir, p);
+    float kh[4], kv[4];
+    const bool sep = factor_taps(sk, kh, kv);
+    const int C4 = p.C >> 2;
+    Tile tl;
+    const bool active = decode_tile(tl, p, C4, (p.out_w + 1) >> 1, p.out_h);
+    if (EPI != EPI_ACT_BWD && !active) return;
+    const int c4 = tl.cv, b = tl.b, oy0 = tl.r0, oy1 = tl.r1;
+    const int ox = 2 * tl.col;
+    const bool colB = ox + 1 < p.out_w;
     const int ix0 = ox - p.pad_x0;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 bsum = zero;
     const float4* xb = x + (int64_t)b * p.in_h * p.in_w * C4 + c4;
     float4* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C4 + c4;
     const float4* rb = reinterpret_cast<const float4*>(ep.ref) + (((int64_t)b * p.out_h) * p.out_w + ox) * C4 + c4;
     float4 bb = zero;
     if (EPI == EPI_BIAS_ACT) bb = *reinterpret_cast<const float4*>(ep.bias + 4 * c4);
-    auto finish = [&](int oy, int col, float4 acc) {
+    auto fin = [&](int oy, int col, float4 acc) {
         const int64_t off = (int64_t)oy * p.out_w * C4 + (int64_t)col * C4;
         if (EPI == EPI_ACT_BWD) {
             const float4 rf = rb[off];
             acc = make_float4(epi_act(acc.x, rf.x, ep.alpha, ep.scale), epi_act(acc.y, rf.y, ep.alpha, ep.scale),
                               epi_act(acc.z, rf.z, ep.alpha, ep.scale), epi_act(acc.w, rf.w, ep.alpha, ep.scale));
             bsum.x += acc.x; bsum.y += acc.y; bsum.z += acc.z; bsum.w += acc.w;
-            if (!active) return;
         }
+        if (EPI == EPI_ACT_BWD && !active) return;       // (the tail lanes: see decode_tile)
         if (EPI == EPI_BIAS_ACT) {
             const float4 v = make_float4(acc.x + bb.x, acc.y + bb.y, acc.z + bb.z, acc.w + bb.w);
             acc = make_float4(epi_act(v.x, v.x, ep.alpha, ep.scale), epi_act(v.y, v.y, ep.alpha, ep.scale),
@@ -445,9 +417,7 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
         }
         yb[off] = acc;
     };
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 5; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
+    const unsigned colmask = col_mask<5>(ix0, p.in_w);
     if (!sep) {      // direct 16-tap form, one output at a time: correct for any FIR, not tuned
 #pragma unroll 1
         for (int oy = oy0; oy < oy1; ++oy)
@@ -467,7 +437,7 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
                         acc.x = fmaf(v.x, kk, acc.x); acc.y = fmaf(v.y, kk, acc.y); acc.z = fmaf(v.z, kk, acc.z); acc.w = fmaf(v.w, kk, acc.w);
                     }
                 }
-                finish(oy, col, acc);
+                fin(oy, col, acc);
             }
         if (EPI == EPI_ACT_BWD) {
             const float part[4] = {bsum.x, bsum.y, bsum.z, bsum.w};
@@ -475,8 +445,7 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
         }
         return;
     }
-    // one input row -> its two horizontally filtered values (columns ox and ox + 1); loads are clamped + masked by value
-    // (component-wise: a ternary on the float4 aggregate becomes a select between ADDRESSES and spills to scratch)
+    // one input row -> its two horizontally filtered values (columns ox and ox + 1); loads clamped + masked as in load_row
     auto hrow = [&](int iy, float4& ha, float4& hb) {
         const bool rowok = (iy >= 0) && (iy < p.in_h);
         const float4* xr = xb + (int64_t)(rowok ? iy : 0) * p.in_w * C4;
@@ -508,460 +477,226 @@ __global__ __launch_bounds__(256) void blur4_f32_c2(float4* __restrict__ y, cons
     for (; oy + 1 < oy1; oy += 2) {      // two output rows per trip: ten 16-byte loads in flight
         hrow(oy - p.pad_y0 + 3, a3, b3);
         hrow(oy - p.pad_y0 + 4, a4, b4);
-        finish(oy, 0, vsum(a0, a1, a2, a3));
-        if (colB) finish(oy, 1, vsum(b0, b1, b2, b3));
-        finish(oy + 1, 0, vsum(a1, a2, a3, a4));
-        if (colB) finish(oy + 1, 1, vsum(b1, b2, b3, b4));
+        fin(oy, 0, vsum(a0, a1, a2, a3));
+        if (colB) fin(oy, 1, vsum(b0, b1, b2, b3));
+        fin(oy + 1, 0, vsum(a1, a2, a3, a4));
+        if (colB) fin(oy + 1, 1, vsum(b1, b2, b3, b4));
         a0 = a2; a1 = a3; a2 = a4; b0 = b2; b1 = b3; b2 = b4;
     }
     if (oy < oy1) {
         hrow(oy - p.pad_y0 + 3, a3, b3);
-        finish(oy, 0, vsum(a0, a1, a2, a3));
-        if (colB) finish(oy, 1, vsum(b0, b1, b2, b3));
+        fin(oy, 0, vsum(a0, a1, a2, a3));
+        if (colB) fin(oy, 1, vsum(b0, b1, b2, b3));
     }
     if (EPI == EPI_ACT_BWD) {
         const float part[4] = {bsum.x, bsum.y, bsum.z, bsum.w};
         bgrad_flush(s_bg, ep.bgrad, p.C, active, 4 * c4, part, 4);
     }
 }
-
-// ---------------- bf16 / f16 NHWC 4x4 blur, 8 channels (16 bytes) per thread ------------------------------------------
-// (E = ideas_bf16 or _Float16: the element type of the 16-byte vectors; arithmetic is f32 for both, see unpack8 / pack8)
-// With 2-byte elements the 4-channel window kernel above moves half the bytes per instruction and is latency-bound
-// (1.45 TB/s measured).  Here a thread owns 8 channels of one output column.  A 4x4 window of 8-channel inputs would be 128
-// registers, so the kernel uses that every FIR on the path is an outer product kv (x) kh (make_kernel, stylegan2/model.py:22-30):
-// each input row is reduced to ONE horizontally filtered row of 8 floats as it arrives, and the window is four of those.
-// The factorisation is checked on the device from the 16 taps; a FIR that is not rank 1 takes the direct 16-tap loop.
-struct F8 { float v[8]; };
-
-template <int EPI, typename E>
-__global__ __launch_bounds__(256) void blur4_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x,
-                                                    const float* __restrict__ fir, FirParams p, FirEpi ep) {
-    __shared__ float sk[16];
-    extern __shared__ float s_bg[];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
-    float kh[4], kv[4];
-    float kmax = 0.f, res = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { kh[t] = sk[t]; kv[t] = sk[0] != 0.f ? sk[4 * t] / sk[0] : 0.f; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { kmax = fmaxf(kmax, fabsf(sk[4 * j + t])); res = fmaxf(res, fabsf(sk[4 * j + t] - kv[j] * kh[t])); }
-    const bool sep = res <= 1e-6f * kmax;           // block-uniform
-
-    const int C8 = p.C >> 3;
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * p.out_w * C8;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < total;
-    if (EPI != EPI_ACT_BWD && !active) return;
-    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int64_t r = active ? i : total - 1;      // (see blur4_nhwc: one path to the barriers of bgrad_flush)
-    const int c8 = (int)(r % C8); r /= C8;
-    const int ox = (int)(r % p.out_w); r /= p.out_w;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
-    const int ix0 = ox - p.pad_x0;
-    const uint4* xb = x + (int64_t)b * p.in_h * p.in_w * C8 + c8;
-    uint4* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C8 + c8;
-    const uint4* rb = reinterpret_cast<const uint4*>(ep.ref) + (((int64_t)b * p.out_h) * p.out_w + ox) * C8 + c8;
-    float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (EPI == EPI_BIAS_ACT) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bb[e] = ep.bias[8 * c8 + e];
-    }
-    // the fused stage of one output vector (the blur is rounded to bf16 first, as the unfused blur -> bias_act path stores it)
-    auto finish = [&](int oy, float (&o)[8]) {
-        if (EPI != EPI_NONE) {
-            const uint4 q = pack8(o, E{});
-            unpack8(q, o, E{});
-        }
-        if (EPI == EPI_ACT_BWD) {
-            float rf[8];
-            unpack8(rb[(int64_t)oy * p.out_w * C8], rf, E{});
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { o[e] = epi_act(o[e], rf[e], ep.alpha, ep.scale); bsum[e] += o[e]; }
-            if (!active) return;
-        }
-        if (EPI == EPI_BIAS_ACT) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float v = o[e] + bb[e]; o[e] = epi_act(v, v, ep.alpha, ep.scale); }
-        }
-        yb[(int64_t)oy * p.out_w * C8] = pack8(o, E{});
-    };
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
-    // (component-wise masking: a ternary on the uint4 aggregate becomes a select between ADDRESSES and spills to scratch)
-    auto load_row = [&](int iy, uint4 (&dst)[4]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const int iyc = rowok ? iy : 0;
-        const uint4* xr = xb + (int64_t)iyc * p.in_w * C8;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const bool ok = rowok && ((colmask >> t) & 1u);
-            const int ixc = ok ? ix0 + t : 0;                      // clamped: always a valid address
-            const uint4 v = xr[(int64_t)ixc * C8];
-            const unsigned m = ok ? 0xffffffffu : 0u;
-            dst[t] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
-        }
-    };
-    if (!sep) {      // direct 16-tap form (no window): correct for any FIR, not tuned
-#pragma unroll 1
-        for (int oy = oy0; oy < oy1; ++oy) {
-            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-            for (int j = 0; j < 4; ++j) {
-                uint4 row[4];
-                load_row(oy - p.pad_y0 + j, row);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float f[8];
-                    unpack8(row[t], f, E{});
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
-                }
-            }
-            finish(oy, acc);
-        }
-        if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, 8 * c8, bsum, 8);
-        return;
-    }
-    auto hfilter = [&](const uint4 (&row)[4], F8& h) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) h.v[e] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            float f[8];
-            unpack8(row[t], f, E{});
-#pragma unroll
-            for (int e = 0; e < 8; ++e) h.v[e] = fmaf(f[e], kh[t], h.v[e]);
-        }
-    };
-    auto emit = [&](int oy, const F8& a0, const F8& a1, const F8& a2, const F8& a3) {
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = a0.v[e] * kv[0] + a1.v[e] * kv[1] + a2.v[e] * kv[2] + a3.v[e] * kv[3];
-        finish(oy, o);
-    };
-    F8 h0, h1, h2, h3, h4;
-    {
-        uint4 r0[4], r1[4], r2[4];
-        const int iy0 = oy0 - p.pad_y0;
-        load_row(iy0 + 0, r0); load_row(iy0 + 1, r1); load_row(iy0 + 2, r2);
-        hfilter(r0, h0); hfilter(r1, h1); hfilter(r2, h2);
-    }
-    int oy = oy0;
-#pragma unroll 1
-    for (; oy + 1 < oy1; oy += 2) {      // two output rows per trip: eight 16-byte loads in flight
-        uint4 ra[4], rb[4];
-        load_row(oy - p.pad_y0 + 3, ra);
-        load_row(oy - p.pad_y0 + 4, rb);
-        hfilter(ra, h3); hfilter(rb, h4);
-        emit(oy, h0, h1, h2, h3);
-        emit(oy + 1, h1, h2, h3, h4);
-        h0 = h2; h1 = h3; h2 = h4;
-    }
-    if (oy < oy1) {
-        uint4 ra[4];
-        load_row(oy - p.pad_y0 + 3, ra);
-        hfilter(ra, h3);
-        emit(oy, h0, h1, h2, h3);
-    }
-    if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, 8 * c8, bsum, 8);
-}
-
-// ---------------- the same, TWO output columns per thread -----------------------------------------------------------------------
-// blur4_bf16x8 issues four 16-byte loads per 16-byte output; a thread that owns the column pair (2q, 2q+1) needs five per row for
-// two outputs (the windows overlap in three columns), i.e. 2.5 loads per output, and keeps two horizontally filtered values per
-// row.  Only for separable FIRs (every FIR of the path; others stay on the one-column kernel).
 template <int EPI, typename E>
 __global__ __launch_bounds__(256) void blur4_bf16x8_c2(uint4* __restrict__ y, const uint4* __restrict__ x,
                                                        const float* __restrict__ fir, FirParams p, FirEpi ep) {
     __shared__ float sk[16];
     extern __shared__ float s_bg[];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
-    float kh[4], kv[4];
-    float kmax = 0.f, res = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { kh[t] = sk[t]; kv[t] = sk[0] != 0.f ? sk[4 * t] / sk[0] : 0.f; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { kmax = fmaxf(kmax, fabsf(sk[4 * j + t])); res = fmaxf(res, fabsf(sk[4 * j + t] - kv[j] * kh[t])); }
-    const bool sep = res <= 1e-6f * kmax;           // block-uniform; a rank > 1 table takes the direct loop below
-    const int C8 = p.C >> 3;
-    const int pw = (p.out_w + 1) >> 1;                       // column pairs
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * pw * C8;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < total;
-    if (EPI != EPI_ACT_BWD && !active) return;
-    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int64_t r = active ? i : total - 1;      // (see blur4_nhwc: one path to the barriers of bgrad_flush)
-    const int c8 = (int)(r % C8); r /= C8;
-    const int q = (int)(r % pw); r /= pw;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int ox = 2 * q;
-    const bool colB = ox + 1 < p.out_w;
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
-    const int ix0 = ox - p.pad_x0;
-    const uint4* xb = x + (int64_t)b * p.in_h * p.in_w * C8 + c8;
-    uint4* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C8 + c8;
-    const uint4* rb = reinterpret_cast<const uint4*>(ep.ref) + (((int64_t)b * p.out_h) * p.out_w + ox) * C8 + c8;
-    float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (EPI == EPI_BIAS_ACT) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bb[e] = ep.bias[8 * c8 + e];
-    }
-    auto finish = [&](int oy, int col, float (&o)[8]) {
-        const int64_t off = (int64_t)oy * p.out_w * C8 + (int64_t)col * C8;
-        if (EPI != EPI_NONE) {
-            const uint4 qv = pack8(o, E{});
-            unpack8(qv, o, E{});
-        }
-        if (EPI == EPI_ACT_BWD) {
-            float rf[8];
-            unpack8(rb[off], rf, E{});
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { o[e] = epi_act(o[e], rf[e], ep.alpha, ep.scale); bsum[e] += o[e]; }
-            if (!active) return;
-        }
-        if (EPI == EPI_BIAS_ACT) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float v = o[e] + bb[e]; o[e] = epi_act(v, v, ep.alpha, ep.scale); }
-        }
-        yb[off] = pack8(o, E{});
-    };
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 5; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
-    if (!sep) {      // direct 16-tap form, one output at a time: correct for any FIR, not tuned
-#pragma unroll 1
-        for (int oy = oy0; oy < oy1; ++oy)
-#pragma unroll 1
-            for (int col = 0; col < (colB ? 2 : 1); ++col) {
-                float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-                for (int j = 0; j < 4; ++j) {
-                    const int iy = oy - p.pad_y0 + j;
-                    if (iy < 0 || iy >= p.in_h) continue;
-#pragma unroll 1
-                    for (int t = 0; t < 4; ++t) {
-                        const int ix = ix0 + col + t;
-                        if (ix < 0 || ix >= p.in_w) continue;
-                        float f[8];
-                        unpack8(xb[((int64_t)iy * p.in_w + ix) * C8], f, E{});
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
-                    }
-                }
-                finish(oy, col, acc);
-            }
-        if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, 8 * c8, bsum, 8);
-        return;
-    }
-    // one input row -> its two horizontally filtered values (columns ox and ox + 1)
-    auto hrow = [&](int iy, F8& ha, F8& hb) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const uint4* xr = xb + (int64_t)(rowok ? iy : 0) * p.in_w * C8;
-        uint4 v[5];
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            const bool ok = rowok && ((colmask >> t) & 1u);
-            const uint4 w = xr[(int64_t)(ok ? ix0 + t : 0) * C8];
-            const unsigned m = ok ? 0xffffffffu : 0u;
-            v[t] = make_uint4(w.x & m, w.y & m, w.z & m, w.w & m);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { ha.v[e] = 0.f; hb.v[e] = 0.f; }
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            float f[8];
-            unpack8(v[t], f, E{});
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if (t < 4) ha.v[e] = fmaf(f[e], kh[t], ha.v[e]);
-                if (t > 0) hb.v[e] = fmaf(f[e], kh[t - 1], hb.v[e]);
-            }
-        }
-    };
-    auto emit = [&](int oy, const F8& a0, const F8& a1, const F8& a2, const F8& a3, const F8& b0, const F8& b1, const F8& b2, const F8& b3) {
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = a0.v[e] * kv[0] + a1.v[e] * kv[1] + a2.v[e] * kv[2] + a3.v[e] * kv[3];
-        finish(oy, 0, o);
-        if (colB) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = b0.v[e] * kv[0] + b1.v[e] * kv[1] + b2.v[e] * kv[2] + b3.v[e] * kv[3];
-            finish(oy, 1, o);
-        }
-    };
-    F8 a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
-    {
-        const int iy0 = oy0 - p.pad_y0;
-        hrow(iy0 + 0, a0, b0); hrow(iy0 + 1, a1, b1); hrow(iy0 + 2, a2, b2);
-    }
-    int oy = oy0;
-#pragma unroll 1
-    for (; oy + 1 < oy1; oy += 2) {      // two output rows per trip: ten 16-byte loads in flight
-        hrow(oy - p.pad_y0 + 3, a3, b3);
-        hrow(oy - p.pad_y0 + 4, a4, b4);
-        emit(oy, a0, a1, a2, a3, b0, b1, b2, b3);
-        emit(oy + 1, a1, a2, a3, a4, b1, b2, b3, b4);
-        a0 = a2; a1 = a3; a2 = a4; b0 = b2; b1 = b3; b2 = b4;
-    }
-    if (oy < oy1) {
-        hrow(oy - p.pad_y0 + 3, a3, b3);
-        emit(oy, a0, a1, a2, a3, b0, b1, b2, b3);
-    }
-    if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, 8 * c8, bsum, 8);
+    blur4_c2<VecX8<E>, EPI>(y, x, fir, p, ep, sk, s_bg);
 }
 
-// ---------------- bf16 / f16 NHWC decimating / zero-stuffing 4x4 FIRs, 8 channels (16 bytes) per thread ------------------------
-// Same reason as blur4_bf16x8: with 2-byte elements the 4-channel kernels above move 8 bytes per lane and instruction and are
-// latency-bound (fir4_up2 / fir4_down2 on bf16: ~1.5 TB/s).  down2 keeps a window of four horizontally filtered rows (the FIR is an
-// outer product; checked on the device, a rank > 1 table takes the direct loop) and advances two input rows per output row; up2
-// keeps the 3 x 3 input neighbourhood of a 2 x 2 output block in registers (72 floats).
+// ---------------- 4x4 blur, up = down = 1, one output column per thread, direct window ---------------------------------------------
+// For the channel counts the 8-channel vectors do not divide (bf16, C % 8 == 4): a thread owns 4 channels of one output column and
+// marches down the rows with a 4x4 register window w[r][t] (input rows iy0..iy0+3 at columns ix0..ix0+3): four loads and one store
+// per output, every access coalesced along C, any FIR.
+template <typename T, int EPI>
+__global__ __launch_bounds__(256) void blur4_nhwc(typename T::raw* __restrict__ y, const typename T::raw* __restrict__ x,
+                                                  const float* __restrict__ fir, FirParams p, FirEpi ep) {
+    typedef typename T::raw raw;
+    constexpr int N = T::N;
+    __shared__ float sk[16];
+    extern __shared__ float s_bg[];
+    stage_taps(sk, fir, p);
+    const int CV = p.C >> T::SHIFT;
+    Tile tl;
+    const bool active = decode_tile(tl, p, CV, p.out_w, p.out_h);
+    if (EPI != EPI_ACT_BWD && !active) return;
+    const int ox = tl.col, oy0 = tl.r0, oy1 = tl.r1;
+    const int ix0 = ox - p.pad_x0;
+    float k[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) k[t] = sk[t];
+    const raw* xb = x + (int64_t)tl.b * p.in_h * p.in_w * CV + tl.cv;
+    raw* yb = y + (((int64_t)tl.b * p.out_h) * p.out_w + ox) * CV + tl.cv;
+    const raw* rb = reinterpret_cast<const raw*>(ep.ref) + (((int64_t)tl.b * p.out_h) * p.out_w + ox) * CV + tl.cv;
+    float bb[N] = {}, bsum[N] = {};
+    if (EPI == EPI_BIAS_ACT) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) bb[e] = ep.bias[N * tl.cv + e];
+    }
+    const unsigned colmask = col_mask<4>(ix0, p.in_w);
+    auto row = [&](int iy, Fv<N> (&dst)[4]) { load_row_f<T, 4>(dst, xb, iy, ix0, colmask, p, CV); };
+    auto emit = [&](int oy, const Fv<N> (&r0)[4], const Fv<N> (&r1)[4], const Fv<N> (&r2)[4], const Fv<N> (&r3)[4]) {
+        float acc[N] = {};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float k0 = k[t], k1 = k[4 + t], k2 = k[8 + t], k3 = k[12 + t];
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc[e] += r0[t].v[e] * k0 + r1[t].v[e] * k1 + r2[t].v[e] * k2 + r3[t].v[e] * k3;
+        }
+        finish<T, EPI>(yb, rb, (int64_t)oy * p.out_w * CV, acc, bb, bsum, ep, active);
+    };
+    Fv<N> w[4][4], w4[4];
+    const int iy0 = oy0 - p.pad_y0;
+    row(iy0 + 0, w[0]);
+    row(iy0 + 1, w[1]);
+    row(iy0 + 2, w[2]);
+    // two output rows per trip: 8 independent loads in flight instead of 4 (the window shift is a dependent chain, so one row per
+    // trip is latency-bound)
+    int oy = oy0;
+    for (; oy + 1 < oy1; oy += 2) {
+        row(oy - p.pad_y0 + 3, w[3]);
+        row(oy - p.pad_y0 + 4, w4);
+        emit(oy, w[0], w[1], w[2], w[3]);
+        emit(oy + 1, w[1], w[2], w[3], w4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { w[0][t] = w[2][t]; w[1][t] = w[3][t]; w[2][t] = w4[t]; }
+    }
+    if (oy < oy1) {
+        row(oy - p.pad_y0 + 3, w[3]);
+        emit(oy, w[0], w[1], w[2], w[3]);
+    }
+    if (EPI == EPI_ACT_BWD) bgrad_flush(s_bg, ep.bgrad, p.C, active, N * tl.cv, bsum, N);
+}
+
+// ---------------- 4x4 FIR with decimation by 2 (up = 1, down = 2) ------------------------------------------------------------------
+// The blur in front of a 1x1 stride-2 skip conv only feeds every second pixel of every second row into the conv
+// (models.py:78-95): computing it at the OUTPUT resolution writes N/4 instead of N and lets the conv run unstrided.
+// Two schemes of different arithmetic, both advancing two input rows per output row (8 loads, 1 store per output):
+//   fir4_down2_nhwc    4 channels per thread (f32, bf16 at C % 8 == 4): the direct 16-tap window of blur4_nhwc;
+//   fir4_down2_bf16x8  8 channels per thread (bf16 / f16 at C % 8 == 0; 8-byte lanes are latency-bound, ~1.5 TB/s): a window of four
+//                      horizontally filtered rows (factor_taps; a rank > 1 table takes the direct loop).
+template <typename T>
+__global__ __launch_bounds__(256) void fir4_down2_nhwc(typename T::raw* __restrict__ y, const typename T::raw* __restrict__ x,
+                                                       const float* __restrict__ fir, FirParams p) {
+    typedef typename T::raw raw;
+    constexpr int N = T::N;
+    __shared__ float sk[16];
+    stage_taps(sk, fir, p);
+    const int CV = p.C >> T::SHIFT;
+    Tile tl;
+    if (!decode_tile(tl, p, CV, p.out_w, p.out_h)) return;
+    const int ix0 = 2 * tl.col - p.pad_x0;
+    float k[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) k[t] = sk[t];
+    const raw* xb = x + (int64_t)tl.b * p.in_h * p.in_w * CV + tl.cv;
+    raw* yb = y + (((int64_t)tl.b * p.out_h) * p.out_w + tl.col) * CV + tl.cv;
+    const unsigned colmask = col_mask<4>(ix0, p.in_w);
+    Fv<N> w[4][4];
+    load_row_f<T, 4>(w[0], xb, 2 * tl.r0 - p.pad_y0 + 0, ix0, colmask, p, CV);
+    load_row_f<T, 4>(w[1], xb, 2 * tl.r0 - p.pad_y0 + 1, ix0, colmask, p, CV);
+    for (int oy = tl.r0; oy < tl.r1; ++oy) {
+        load_row_f<T, 4>(w[2], xb, 2 * oy - p.pad_y0 + 2, ix0, colmask, p, CV);
+        load_row_f<T, 4>(w[3], xb, 2 * oy - p.pad_y0 + 3, ix0, colmask, p, CV);
+        float acc[N] = {};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int e = 0; e < N; ++e) acc[e] = fmaf(w[j][t].v[e], k[4 * j + t], acc[e]);
+        yb[(int64_t)oy * p.out_w * CV] = T::pack(acc);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { w[0][t] = w[2][t]; w[1][t] = w[3][t]; }
+    }
+}
+
 template <typename E>
 __global__ __launch_bounds__(256) void fir4_down2_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x,
                                                          const float* __restrict__ fir, FirParams p) {
+    typedef VecX8<E> T;
+    constexpr int N = T::N;
     __shared__ float sk[16];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
+    stage_taps(sk, fir, p);
     float kh[4], kv[4];
-    float kmax = 0.f, res = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { kh[t] = sk[t]; kv[t] = sk[0] != 0.f ? sk[4 * t] / sk[0] : 0.f; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { kmax = fmaxf(kmax, fabsf(sk[4 * j + t])); res = fmaxf(res, fabsf(sk[4 * j + t] - kv[j] * kh[t])); }
-    const bool sep = res <= 1e-6f * kmax;           // block-uniform
-    const int C8 = p.C >> 3;
-    const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * p.out_w * C8;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int64_t r = i;
-    const int c8 = (int)(r % C8); r /= C8;
-    const int ox = (int)(r % p.out_w); r /= p.out_w;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int oy0 = seg * p.seg_rows;
-    const int oy1 = (oy0 + p.seg_rows < p.out_h) ? oy0 + p.seg_rows : p.out_h;
-    const int ix0 = 2 * ox - p.pad_x0;
-    const uint4* xb = x + (int64_t)b * p.in_h * p.in_w * C8 + c8;
-    uint4* yb = y + (((int64_t)b * p.out_h) * p.out_w + ox) * C8 + c8;
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) colmask |= ((ix0 + t >= 0) && (ix0 + t < p.in_w)) ? (1u << t) : 0u;
-    auto load_row = [&](int iy, uint4 (&dst)[4]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const uint4* xr = xb + (int64_t)(rowok ? iy : 0) * p.in_w * C8;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const bool ok = rowok && ((colmask >> t) & 1u);
-            const uint4 v = xr[(int64_t)(ok ? ix0 + t : 0) * C8];
-            const unsigned m = ok ? 0xffffffffu : 0u;
-            dst[t] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
-        }
-    };
+    const bool sep = factor_taps(sk, kh, kv);
+    const int CV = p.C >> T::SHIFT;
+    Tile tl;
+    if (!decode_tile(tl, p, CV, p.out_w, p.out_h)) return;
+    const int ix0 = 2 * tl.col - p.pad_x0;
+    const uint4* xb = x + (int64_t)tl.b * p.in_h * p.in_w * CV + tl.cv;
+    uint4* yb = y + (((int64_t)tl.b * p.out_h) * p.out_w + tl.col) * CV + tl.cv;
+    const unsigned colmask = col_mask<4>(ix0, p.in_w);
     if (!sep) {      // direct 16-tap form: correct for any FIR, not tuned
 #pragma unroll 1
-        for (int oy = oy0; oy < oy1; ++oy) {
-            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int oy = tl.r0; oy < tl.r1; ++oy) {
+            float acc[N] = {};
 #pragma unroll 1
             for (int j = 0; j < 4; ++j) {
-                uint4 row[4];
-                load_row(2 * oy - p.pad_y0 + j, row);
+                Fv<N> row[4];
+                load_row_f<T, 4>(row, xb, 2 * oy - p.pad_y0 + j, ix0, colmask, p, CV);
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float f[8];
-                    unpack8(row[t], f, E{});
+                for (int t = 0; t < 4; ++t)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] = fmaf(f[e], sk[4 * j + t], acc[e]);
-                }
+                    for (int e = 0; e < N; ++e) acc[e] = fmaf(row[t].v[e], sk[4 * j + t], acc[e]);
             }
-            yb[(int64_t)oy * p.out_w * C8] = pack8(acc, E{});
+            yb[(int64_t)oy * p.out_w * CV] = T::pack(acc);
         }
         return;
     }
-    auto hfilter = [&](const uint4 (&row)[4], F8& h) {
+    auto hfilter = [&](const uint4 (&row)[4], Fv<N>& h) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h.v[e] = 0.f;
+        for (int e = 0; e < N; ++e) h.v[e] = 0.f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            float f[8];
-            unpack8(row[t], f, E{});
+            float f[N];
+            T::unpack(row[t], f);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) h.v[e] = fmaf(f[e], kh[t], h.v[e]);
+            for (int e = 0; e < N; ++e) h.v[e] = fmaf(f[e], kh[t], h.v[e]);
         }
     };
-    F8 h0, h1, h2, h3;
-    {
-        uint4 r0[4], r1[4];
-        load_row(2 * oy0 - p.pad_y0 + 0, r0);
-        load_row(2 * oy0 - p.pad_y0 + 1, r1);
-        hfilter(r0, h0); hfilter(r1, h1);
-    }
-#pragma unroll 1
-    for (int oy = oy0; oy < oy1; ++oy) {
+    auto rows2 = [&](int iy, Fv<N>& ha, Fv<N>& hb) {      // input rows iy, iy + 1 -> their horizontally filtered values; 8 loads in flight
         uint4 ra[4], rb[4];
-        load_row(2 * oy - p.pad_y0 + 2, ra);
-        load_row(2 * oy - p.pad_y0 + 3, rb);
-        hfilter(ra, h2); hfilter(rb, h3);
-        float o[8];
+        load_row<T, 4>(ra, xb, iy, ix0, colmask, p, CV);
+        load_row<T, 4>(rb, xb, iy + 1, ix0, colmask, p, CV);
+        hfilter(ra, ha); hfilter(rb, hb);
+    };
+    Fv<N> h0, h1, h2, h3;
+    rows2(2 * tl.r0 - p.pad_y0, h0, h1);
+#pragma unroll 1
+    for (int oy = tl.r0; oy < tl.r1; ++oy) {
+        rows2(2 * oy - p.pad_y0 + 2, h2, h3);
+        float o[N];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = h0.v[e] * kv[0] + h1.v[e] * kv[1] + h2.v[e] * kv[2] + h3.v[e] * kv[3];
-        yb[(int64_t)oy * p.out_w * C8] = pack8(o, E{});
+        for (int e = 0; e < N; ++e) o[e] = dot4(h0.v[e], h1.v[e], h2.v[e], h3.v[e], kv[0], kv[1], kv[2], kv[3]);
+        yb[(int64_t)oy * p.out_w * CV] = T::pack(o);
         h0 = h2; h1 = h3;
     }
 }
 
-template <typename E>
-__global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, const uint4* __restrict__ x, const float* __restrict__ fir,
-                                                       FirParams p, const uint4* __restrict__ resid) {
+// ---------------- 4x4 FIR after zero-stuffing by 2 (up = 2, down = 1) ---------------------------------------------------------------
+// The adjoint of the kernels above (their backward), and the blur behind a 1x1 stride-2 TRANSPOSED skip conv (three of four
+// pixels of that conv's output are structural zeros; here they are never written or read).  Per axis, output o = 2i + a
+// (a = 0, 1) sees the two taps k = k0(a), k0(a) + 2 with k0(a) = (pad0 - a) & 1, at inputs i + d(a), i + d(a) + 1,
+// d(a) = (a + k0(a) - pad0) / 2 -- so a 2 x 2 output block needs a 3 x 3 input neighbourhood, kept in registers (72 floats at 8
+// channels).  A thread owns the output column pair (2j, 2j + 1) of one channel vector and marches down block rows: 3 loads and 4
+// stores per block row.  Never assumes separability.
+// `resid` (optional, same shape as y): y = fir(x) + resid -- the residual merge behind an upsampling skip, and (as the adjoint of
+// fir4_down2) the sum of the two input gradients of a downsampling ResBlock, without a separate add pass (ideas_fir_up2_add).
+template <typename T>
+__global__ __launch_bounds__(256) void fir4_up2(typename T::raw* __restrict__ y, const typename T::raw* __restrict__ x,
+                                                const float* __restrict__ fir, FirParams p, const typename T::raw* __restrict__ resid) {
+    typedef typename T::raw raw;
+    constexpr int N = T::N;
     __shared__ float sk[16];
-    if (threadIdx.x < 16) {
-        const int t = threadIdx.x;
-        sk[t] = fir[p.flip ? 15 - t : t] * p.gain;
-    }
-    __syncthreads();
-    const int C8 = p.C >> 3;
+    stage_taps(sk, fir, p);
+    const int CV = p.C >> T::SHIFT;
     const int bh = (p.out_h + 1) >> 1, bw = (p.out_w + 1) >> 1;          // 2 x 2 output blocks
-    const int segs = (bh + p.seg_rows - 1) / p.seg_rows;
-    const int64_t total = (int64_t)p.B * segs * bw * C8;
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    int64_t r = idx;
-    const int c8 = (int)(r % C8); r /= C8;
-    const int j = (int)(r % bw); r /= bw;
-    const int seg = (int)(r % segs);
-    const int b = (int)(r / segs);
-    const int i0 = seg * p.seg_rows;
-    const int i1 = (i0 + p.seg_rows < bh) ? i0 + p.seg_rows : bh;
-    // per-axis tap / offset tables (a = output parity), as in fir4_up2_nhwc
+    Tile tl;
+    if (!decode_tile(tl, p, CV, bw, bh)) return;
+    const int j = tl.col;
+    // per-axis tap / offset tables (a = output parity)
     const int ky0[2] = {p.pad_y0 & 1, (p.pad_y0 - 1) & 1}, kx0[2] = {p.pad_x0 & 1, (p.pad_x0 - 1) & 1};
     const int dy[2] = {(ky0[0] - p.pad_y0) >> 1, (1 + ky0[1] - p.pad_y0) >> 1};
     const int dx[2] = {(kx0[0] - p.pad_x0) >> 1, (1 + kx0[1] - p.pad_x0) >> 1};
-    const int ey = dy[1] - dy[0], ex = dx[1] - dx[0];
+    const int ey = dy[1] - dy[0], ex = dx[1] - dx[0];                       // 0 or 1: which 2 of the 3 rows / columns parity 1 uses
     float wq[2][2][2][2];                                                  // [a][bb][u][v]
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -971,57 +706,43 @@ __global__ __launch_bounds__(256) void fir4_up2_bf16x8(uint4* __restrict__ y, co
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int v = 0; v < 2; ++v) wq[a][bb][u][v] = sk[(ky0[a] + 2 * u) * 4 + kx0[bb] + 2 * v];
-    const uint4* xb = x + (int64_t)b * p.in_h * p.in_w * C8 + c8;
+    const raw* xb = x + (int64_t)tl.b * p.in_h * p.in_w * CV + tl.cv;
     const int cx0 = j + dx[0];
-    unsigned colmask = 0;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) colmask |= ((cx0 + t >= 0) && (cx0 + t < p.in_w)) ? (1u << t) : 0u;
-    auto load_row = [&](int iy, F8 (&dst)[3]) {
-        const bool rowok = (iy >= 0) && (iy < p.in_h);
-        const uint4* xr = xb + (int64_t)(rowok ? iy : 0) * p.in_w * C8;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const bool ok = rowok && ((colmask >> t) & 1u);
-            const uint4 v = xr[(int64_t)(ok ? cx0 + t : 0) * C8];
-            const unsigned m = ok ? 0xffffffffu : 0u;
-            unpack8(make_uint4(v.x & m, v.y & m, v.z & m, v.w & m), dst[t].v, E{});
-        }
-    };
-    F8 R0[3], R1[3], R2[3];
-    load_row(i0 + dy[0] + 0, R0);
-    load_row(i0 + dy[0] + 1, R1);
+    const unsigned colmask = col_mask<3>(cx0, p.in_w);
+    Fv<N> R0[3], R1[3], R2[3];
+    load_row_f<T, 3>(R0, xb, tl.r0 + dy[0] + 0, cx0, colmask, p, CV);
+    load_row_f<T, 3>(R1, xb, tl.r0 + dy[0] + 1, cx0, colmask, p, CV);
     const bool colB = 2 * j + 1 < p.out_w;
 #pragma unroll 1
-    for (int i = i0; i < i1; ++i) {
-        load_row(i + dy[0] + 2, R2);
+    for (int i = tl.r0; i < tl.r1; ++i) {
+        load_row_f<T, 3>(R2, xb, i + dy[0] + 2, cx0, colmask, p, CV);
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const int oy = 2 * i + a;
             if (oy >= p.out_h) break;
-            const bool hi = (a == 1) && (ey == 1);
+            const bool hi = (a == 1) && (ey == 1);      // rows of this parity: R[ra], R[ra + 1] with ra = a ? ey : 0 (no dynamic register indexing)
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb) {
                 if (bb == 1 && !colB) break;
                 const bool hx = (bb == 1) && (ex == 1);
                 const float w00 = wq[a][bb][0][0], w01 = wq[a][bb][0][1], w10 = wq[a][bb][1][0], w11 = wq[a][bb][1][1];
-                float o[8];
+                float o[N];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
+                for (int e = 0; e < N; ++e) {
                     const float top0 = hi ? R1[0].v[e] : R0[0].v[e], top1 = hi ? R1[1].v[e] : R0[1].v[e], top2 = hi ? R1[2].v[e] : R0[2].v[e];
                     const float bot0 = hi ? R2[0].v[e] : R1[0].v[e], bot1 = hi ? R2[1].v[e] : R1[1].v[e], bot2 = hi ? R2[2].v[e] : R1[2].v[e];
                     const float t0 = hx ? top1 : top0, t1 = hx ? top2 : top1, b0 = hx ? bot1 : bot0, b1 = hx ? bot2 : bot1;
-                    o[e] = t0 * w00 + t1 * w01 + b0 * w10 + b1 * w11;
+                    o[e] = dot4(t0, t1, b0, b1, w00, w01, w10, w11);
                 }
-                const int64_t yi = (((int64_t)b * p.out_h + oy) * p.out_w + 2 * j + bb) * C8 + c8;
+                const int64_t yi = (((int64_t)tl.b * p.out_h + oy) * p.out_w + 2 * j + bb) * CV + tl.cv;
                 if (resid) {
-                    const uint4 q = pack8(o, E{});          // the two-kernel chain stores the FIR (bf16) first
-                    unpack8(q, o, E{});
-                    float rf[8];
-                    unpack8(resid[yi], rf, E{});
+                    T::round(o);          // the two-kernel chain stores the FIR first
+                    float rf[N];
+                    T::unpack(resid[yi], rf);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] += rf[e];
+                    for (int e = 0; e < N; ++e) o[e] += rf[e];
                 }
-                y[yi] = pack8(o, E{});
+                y[yi] = T::pack(o);
             }
         }
 #pragma unroll
@@ -1080,6 +801,10 @@ __global__ __launch_bounds__(256) void blur_nchw_tile(T* __restrict__ y, const T
 
 }  // namespace
 
+// one thread per tile: 256-thread blocks over `total` threads
+#define FIR_LAUNCH(kernel, total, lds, stream, ...) \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ideas_cdiv((int64_t)(total), 256)), dim3(256), lds, stream, __VA_ARGS__)
+
 // the unit-stride 4x4 NHWC blur (+ fused stage): shared by ideas_upfirdn2d (EPI_NONE) and ideas_blur_fused
 template <int EPI>
 static int launch_blur4(void* y, const void* x, const float* fir, FirParams p, FirEpi ep, int dtype, hipStream_t stream) {
@@ -1088,42 +813,48 @@ static int launch_blur4(void* y, const void* x, const float* fir, FirParams p, F
     p.seg_rows = 16;
     const int segs = (p.out_h + p.seg_rows - 1) / p.seg_rows;
     const int64_t total = (int64_t)p.B * segs * p.out_w * (p.C / 4);
-    const int64_t grid = ideas_cdiv(total, 256);
-    if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
+    if (ideas_cdiv(total, 256) > 0x7fffffffLL) return IDEAS_E_SHAPE;
     const size_t lds = EPI == EPI_ACT_BWD ? (size_t)p.C * sizeof(float) : 0;
-#ifndef IDEAS_BLUR_C2
-#define IDEAS_BLUR_C2 1
-#endif
+    const int64_t pairs = (int64_t)p.B * segs * ((p.out_w + 1) / 2);          // column pairs: the two-column kernels
     if constexpr (EPI == EPI_NONE) {          // f16 (C % 8 == 0, plain blur only): the 8-channel two-column kernel of bf16
         if (dtype == IDEAS_F16) {
-            const int64_t total8 = (int64_t)p.B * segs * ((p.out_w + 1) / 2) * (p.C / 8);
-            hipLaunchKernelGGL((blur4_bf16x8_c2<EPI, _Float16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream,
-                               (uint4*)y, (const uint4*)x, fir, p, ep);
+            FIR_LAUNCH((blur4_bf16x8_c2<EPI, _Float16>), pairs * (p.C / 8), lds, stream, (uint4*)y, (const uint4*)x, fir, p, ep);
             return ideas_launch_status();
         }
     }
-    if (IDEAS_BLUR_C2 && dtype == IDEAS_BF16 && p.C % 8 == 0) {
-        const int64_t total8 = (int64_t)p.B * segs * ((p.out_w + 1) / 2) * (p.C / 8);
-        hipLaunchKernelGGL((blur4_bf16x8_c2<EPI, ideas_bf16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
-                           (const uint4*)x, fir, p, ep);
-        return ideas_launch_status();
-    }
-    if (dtype == IDEAS_BF16 && p.C % 8 == 0) {
-        const int64_t total8 = (int64_t)p.B * segs * p.out_w * (p.C / 8);
-        hipLaunchKernelGGL((blur4_bf16x8<EPI, ideas_bf16>), dim3((unsigned)ideas_cdiv(total8, 256)), dim3(256), lds, stream, (uint4*)y,
-                           (const uint4*)x, fir, p, ep);
-    } else if (dtype == IDEAS_BF16)
-        hipLaunchKernelGGL((blur4_nhwc<ideas_bf16x4, EPI>), dim3((unsigned)grid), dim3(256), lds, stream, (ideas_bf16x4*)y,
-                           (const ideas_bf16x4*)x, fir, p, ep);
-    else if (IDEAS_BLUR_C2) {
-        const int64_t total2 = (int64_t)p.B * segs * ((p.out_w + 1) / 2) * (p.C / 4);
-        hipLaunchKernelGGL(blur4_f32_c2<EPI>, dim3((unsigned)ideas_cdiv(total2, 256)), dim3(256), lds, stream, (float4*)y,
-                           (const float4*)x, fir, p, ep);
-    } else
-        hipLaunchKernelGGL((blur4_nhwc<float4, EPI>), dim3((unsigned)grid), dim3(256), lds, stream, (float4*)y, (const float4*)x, fir,
-                           p, ep);
+    if (dtype == IDEAS_BF16 && p.C % 8 == 0)
+        FIR_LAUNCH((blur4_bf16x8_c2<EPI, ideas_bf16>), pairs * (p.C / 8), lds, stream, (uint4*)y, (const uint4*)x, fir, p, ep);
+    else if (dtype == IDEAS_BF16)
+        FIR_LAUNCH((blur4_nhwc<VecBf16x4, EPI>), total, lds, stream, (ideas_bf16x4*)y, (const ideas_bf16x4*)x, fir, p, ep);
+    else
+        FIR_LAUNCH(blur4_f32_c2<EPI>, pairs * (p.C / 4), lds, stream, (float4*)y, (const float4*)x, fir, p, ep);
     return ideas_launch_status();
 }
+
+// down = 2 / up = 2: `tiles` = batch x row segments x columns (column pairs for up = 2); x8: 8 channels per thread (bf16 / f16)
+static void launch_down2(void* y, const void* x, const float* fir, const FirParams& p, int64_t tiles, int dtype, bool x8, hipStream_t stream) {
+    if (x8 && dtype == IDEAS_F16)
+        FIR_LAUNCH(fir4_down2_bf16x8<_Float16>, tiles * (p.C / 8), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
+    else if (x8)
+        FIR_LAUNCH(fir4_down2_bf16x8<ideas_bf16>, tiles * (p.C / 8), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
+    else if (dtype == IDEAS_BF16)
+        FIR_LAUNCH(fir4_down2_nhwc<VecBf16x4>, tiles * (p.C / 4), 0, stream, (ideas_bf16x4*)y, (const ideas_bf16x4*)x, fir, p);
+    else
+        FIR_LAUNCH(fir4_down2_nhwc<VecF32>, tiles * (p.C / 4), 0, stream, (float4*)y, (const float4*)x, fir, p);
+}
+static void launch_up2(void* y, const void* x, const float* fir, const FirParams& p, const void* resid, int64_t tiles, int dtype, bool x8,
+                       hipStream_t stream) {
+    if (x8 && dtype == IDEAS_F16)
+        FIR_LAUNCH(fir4_up2<VecX8<_Float16>>, tiles * (p.C / 8), 0, stream, (uint4*)y, (const uint4*)x, fir, p, (const uint4*)resid);
+    else if (x8)
+        FIR_LAUNCH(fir4_up2<VecX8<ideas_bf16>>, tiles * (p.C / 8), 0, stream, (uint4*)y, (const uint4*)x, fir, p, (const uint4*)resid);
+    else if (dtype == IDEAS_BF16)
+        FIR_LAUNCH(fir4_up2<VecBf16x4>, tiles * (p.C / 4), 0, stream, (ideas_bf16x4*)y, (const ideas_bf16x4*)x, fir, p, (const ideas_bf16x4*)resid);
+    else
+        FIR_LAUNCH(fir4_up2<VecF32>, tiles * (p.C / 4), 0, stream, (float4*)y, (const float4*)x, fir, p, (const float4*)resid);
+}
+
+#undef FIR_LAUNCH
 
 extern "C" int ideas_blur_fused(void* y, const void* x, const float* fir, int B, int C, int in_h, int in_w, int out_h, int out_w,
                                 int pad_x0, int pad_y0, float gain, int flip, int mode, const void* ref, const float* bias,
@@ -1172,18 +903,9 @@ static int upfirdn2d_impl(void* y, const void* x, const float* fir, int B, int C
     if (vec4 && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2) {
         p.seg_rows = out_h >= 64 ? 16 : 8;
         const int segs = (out_h + p.seg_rows - 1) / p.seg_rows;
-        const int64_t grid = ideas_cdiv((int64_t)B * segs * out_w * (C / 4), 256);
-        if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
-        const unsigned grid8 = (unsigned)ideas_cdiv((int64_t)B * segs * out_w * (C / 8), 256);
-        if (x8 && dtype == IDEAS_F16)
-            hipLaunchKernelGGL(fir4_down2_bf16x8<_Float16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
-        else if (x8)
-            hipLaunchKernelGGL(fir4_down2_bf16x8<ideas_bf16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p);
-        else if (dtype == IDEAS_BF16)
-            hipLaunchKernelGGL(fir4_down2_nhwc<ideas_bf16x4>, dim3((unsigned)grid), dim3(256), 0, stream, (ideas_bf16x4*)y,
-                               (const ideas_bf16x4*)x, fir, p);
-        else
-            hipLaunchKernelGGL(fir4_down2_nhwc<float4>, dim3((unsigned)grid), dim3(256), 0, stream, (float4*)y, (const float4*)x, fir, p);
+        const int64_t tiles = (int64_t)B * segs * out_w;
+        if (ideas_cdiv(tiles * (C / 4), 256) > 0x7fffffffLL) return IDEAS_E_SHAPE;
+        launch_down2(y, x, fir, p, tiles, dtype, x8, stream);
         return ideas_launch_status();
     }
     if (resid && !(vec4 && up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && ideas_aligned16(resid))) return IDEAS_E_UNSUPPORTED;
@@ -1191,21 +913,9 @@ static int upfirdn2d_impl(void* y, const void* x, const float* fir, int B, int C
         const int bh = (out_h + 1) / 2, bw = (out_w + 1) / 2;
         p.seg_rows = bh >= 64 ? 16 : 8;
         const int segs = (bh + p.seg_rows - 1) / p.seg_rows;
-        const int64_t grid = ideas_cdiv((int64_t)B * segs * bw * (C / 4), 256);
-        if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;
-        const unsigned grid8 = (unsigned)ideas_cdiv((int64_t)B * segs * bw * (C / 8), 256);
-        if (x8 && dtype == IDEAS_F16)
-            hipLaunchKernelGGL(fir4_up2_bf16x8<_Float16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p,
-                               (const uint4*)resid);
-        else if (x8)
-            hipLaunchKernelGGL(fir4_up2_bf16x8<ideas_bf16>, dim3(grid8), dim3(256), 0, stream, (uint4*)y, (const uint4*)x, fir, p,
-                               (const uint4*)resid);
-        else if (dtype == IDEAS_BF16)
-            hipLaunchKernelGGL(fir4_up2_nhwc<ideas_bf16x4>, dim3((unsigned)grid), dim3(256), 0, stream, (ideas_bf16x4*)y,
-                               (const ideas_bf16x4*)x, fir, p, (const ideas_bf16x4*)resid);
-        else
-            hipLaunchKernelGGL(fir4_up2_nhwc<float4>, dim3((unsigned)grid), dim3(256), 0, stream, (float4*)y, (const float4*)x, fir, p,
-                               (const float4*)resid);
+        const int64_t tiles = (int64_t)B * segs * bw;
+        if (ideas_cdiv(tiles * (C / 4), 256) > 0x7fffffffLL) return IDEAS_E_SHAPE;
+        launch_up2(y, x, fir, p, resid, tiles, dtype, x8, stream);
         return ideas_launch_status();
     }
     if (unit && layout == IDEAS_NCHW && kh <= 4 && kw <= 4 && (dtype == IDEAS_F32 || dtype == IDEAS_F16)) {

@@ -129,13 +129,13 @@ def test_upfirdn2d_random_with_double_backward(ops, shape, pad, gain, cl):
 @pytest.mark.parametrize("case", [((2, 8, 32, 32), 1, 2, (1, 1)), ((2, 12, 33, 31), 1, 2, (2, 2)), ((1, 64, 64, 64), 1, 2, (1, 1)),
                                   ((2, 8, 16, 16), 2, 1, (2, 1)), ((2, 12, 17, 15), 2, 1, (2, 2)), ((1, 64, 32, 32), 2, 1, (2, 1)),
                                   ((2, 4, 9, 9), 2, 1, (1, 1)), ((2, 4, 5, 7), 2, 1, (3, 2)), ((2, 4, 10, 6), 1, 2, (0, 3)),
-                                  # 8-channel multiples: the bf16 fir4_down2_bf16x8 / fir4_up2_bf16x8 kernels on odd sizes / pads
+                                  # 8-channel multiples: the bf16 fir4_down2_bf16x8 / fir4_up2<VecX8> kernels on odd sizes / pads
                                   ((2, 16, 17, 15), 2, 1, (2, 2)), ((2, 8, 5, 7), 2, 1, (3, 2)), ((2, 8, 10, 6), 1, 2, (0, 3)),
                                   ((2, 16, 33, 31), 1, 2, (2, 2)), ((1, 8, 9, 9), 2, 1, (1, 1))])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_fir_at_output_resolution_vs_oracle(ops, case, bf16):
     """The decimating (down = 2) and zero-stuffing (up = 2) 4x4 FIR kernels behind the 1x1 stride-2 skip convs (csrc/upfirdn2d.hip
-    fir4_down2_nhwc / fir4_up2_nhwc), every pad parity and odd sizes, forward + backward + double backward vs the f64 oracle."""
+    fir4_down2_nhwc / fir4_up2), every pad parity and odd sizes, forward + backward + double backward vs the f64 oracle."""
     shape, up, down, pad = case
     torch.manual_seed(sum(shape) + up + 3 * down + pad[0])
     k = O.make_kernel((1, 3, 3, 1)) * (up * up)
@@ -160,7 +160,7 @@ def test_fir_at_output_resolution_vs_oracle(ops, case, bf16):
 @pytest.mark.parametrize("up,down,pad", [(1, 2, (2, 1)), (2, 1, (2, 1))])
 def test_bf16_fir_kernels_take_a_non_separable_fir(ops, up, down, pad):
     """fir4_down2_bf16x8 uses the outer-product structure of make_kernel's tables; a rank > 1 FIR must take its direct loop (and
-    fir4_up2_bf16x8 never assumes separability): random 4x4 taps against the f64 oracle."""
+    fir4_up2 never assumes separability): random 4x4 taps against the f64 oracle."""
     torch.manual_seed(21)
     k = torch.randn(4, 4)
     x = torch.randn(2, 16, 14, 10).to(torch.bfloat16)

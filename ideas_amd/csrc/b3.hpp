@@ -11,7 +11,6 @@ namespace {
 
 constexpr int BK = 16;     // f32 K depth of one pipeline step = K of one bf16 MFMA
 constexpr int ROWB = 32;   // bytes per LDS row (16 bf16)
-constexpr unsigned RSRC_FLAGS = 0x00020000u;   // raw buffer, 32-bit data format
 
 // The staging arithmetic that runs beside MFMAs (the residuals of the split, the modulation scale, the FIR sum of conv_b3_s2fir.hip) as single-issue instructions
 // (common.hpp::sub1 / mul1 / fma1).  A translation unit whose kernels measured no gain from it defines B3_UNPACK_F32 0 before including

@@ -122,6 +122,15 @@ template <> struct vec_io<ideas_f16x8> {
     }
 };
 
+__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+// component-wise select: a ternary on the float4 aggregates becomes a select between two ADDRESSES, which forces
+// the staging registers into scratch memory (seen in the ISA as scratch_store + vmcnt(0) after every load)
+__device__ __forceinline__ float4 keep4(bool ok, float4 v) {
+    return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+}
+
+constexpr unsigned RSRC_FLAGS = 0x00020000u;   // buffer resource word 3 of the raw buffer accesses: 32-bit data format
+
 // mirror an out-of-range coordinate back into [0,n) (ReflectionPad2d semantics, no edge repeat)
 __device__ __forceinline__ int reflect_coord(int i, int n) {
     if (i < 0) i = -i;

@@ -34,6 +34,7 @@
 //  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
+#include "conv_epilogue.hpp"
 #include <type_traits>
 
 namespace {
@@ -297,23 +298,10 @@ __device__ __forceinline__ void conv_b3_body(float* __restrict__ y, const float*
     }
     if (kt < nk) step(kt, st0, st1);
 
-    // ---- epilogue (identical to conv_igemm_kernel) -------------------------------------------------------------
+    // ---- epilogue: row table in LDS, then the f32 rule of conv_epilogue.hpp --------------------------------------
     int64_t* row_off = reinterpret_cast<int64_t*>(smem);
     int* row_b = reinterpret_cast<int*>(smem + 8 * BM);
-    if (t < BM) {
-        const int64_t m = m0 + t;
-        int64_t off = -1;
-        int b = 0;
-        if (m < M) {
-            const int ox = (int)(m % p.OW);
-            const int64_t q = m / p.OW;
-            const int oy = (int)(q % p.OH);
-            b = (int)(q / p.OH);
-            off = (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout;
-        }
-        row_off[t] = off;
-        row_b[t] = b;
-    }
+    epi_row_table(row_off, row_b, t, BM, m0, M, p);
     __syncthreads();
 #pragma unroll
     for (int b = 0; b < NT; ++b) {
@@ -327,12 +315,9 @@ __device__ __forceinline__ void conv_b3_body(float* __restrict__ y, const float*
                 const int row = (wm * MT + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 const int64_t off = row_off[row];
                 if (off < 0) continue;
-                float v = mul_rn(acc[a][b][r], p.gain);
-                if (out_scale) v = mul_rn(v, out_scale[(int64_t)row_b[row] * p.Cout + n]);
-                v = mul_then_add(v, 1.0f, bv);
-                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                if (resid) v = (v + resid[off + n]) * p.resid_gain;
-                if (p.accumulate) y[off + n] += v; else y[off + n] = v;
+                float v = epi_head(acc[a][b][r], p, out_scale, (int64_t)row_b[row] * p.Cout + n, bv);
+                if (resid) v = epi_resid(v, resid[off + n], p);
+                epi_store(y, off + n, v, p.accumulate);
             }
         }
     }

@@ -22,6 +22,7 @@
 //  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
+#include "conv_epilogue.hpp"
 #include <cstdlib>
 
 namespace {
@@ -145,10 +146,8 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pw_kernel(float* __restrict__ 
                             for (int k = 0; k < 4; ++k) off[k] = ybase + (unsigned)(a * 32 + k + 8 * e4) * cout4;
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
-                                float v = mul_rn(acc[a][4 * e4 + k], p.gain);
-                                v = mul_then_add(v, 1.0f, bv);
-                                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                                if (resid) v = (v + __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)off[k], 0, 0))) * p.resid_gain;
+                                float v = epi_head(acc[a][4 * e4 + k], p, bv);
+                                if (resid) v = epi_resid(v, __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)off[k], 0, 0)), p);
                                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)off[k], 0, 0);
                             }
                             __builtin_amdgcn_sched_barrier(0);
@@ -163,10 +162,8 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pw_kernel(float* __restrict__ 
                     }
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        float v = mul_rn(acc[a][e], p.gain);
-                        v = mul_then_add(v, 1.0f, bv);
-                        if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                        if (resid) v = (v + rv[e]) * p.resid_gain;
+                        float v = epi_head(acc[a][e], p, bv);
+                        if (resid) v = epi_resid(v, rv[e], p);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)ybase,
                                                               (int)((unsigned)(a * 32 + (e & 3) + 8 * (e >> 2)) * cout4), 0);
                     }
@@ -344,10 +341,8 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pwk_kernel(float* __restrict__
                             for (int k = 0; k < 4; ++k) off[k] = ybase + (unsigned)(a * 32 + k + 8 * e4) * cout4;
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
-                                float v = mul_rn(acc[np][a][4 * e4 + k], p.gain);
-                                v = mul_then_add(v, 1.0f, bv);
-                                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                                if (resid) v = (v + __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)off[k], 0, 0))) * p.resid_gain;
+                                float v = epi_head(acc[np][a][4 * e4 + k], p, bv);
+                                if (resid) v = epi_resid(v, __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)off[k], 0, 0)), p);
                                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)off[k], 0, 0);
                             }
                             __builtin_amdgcn_sched_barrier(0);
@@ -362,10 +357,8 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pwk_kernel(float* __restrict__
                     }
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        float v = mul_rn(acc[np][a][e], p.gain);
-                        v = mul_then_add(v, 1.0f, bv);
-                        if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                        if (resid) v = (v + rv[e]) * p.resid_gain;
+                        float v = epi_head(acc[np][a][e], p, bv);
+                        if (resid) v = epi_resid(v, rv[e], p);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)ybase,
                                                               (int)((unsigned)(a * 32 + (e & 3) + 8 * (e >> 2)) * cout4), 0);
                     }

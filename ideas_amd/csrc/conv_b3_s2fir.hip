@@ -25,6 +25,7 @@
 // (conv_b3_wgrad.hip reads it as before).  Measurements, the ablations behind this shape and what the fusion can and cannot buy:
 // DESIGN.md section 3.9.
 #include "b3.hpp"
+#include "conv_epilogue.hpp"
 #ifndef S2FIR_DPP_BUILTIN
 #define S2FIR_DPP_BUILTIN 0
 #endif
@@ -359,7 +360,7 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
     for (int c = 0; c < nc; ++c) step(c);
 #undef SB
 
-    // ---- epilogue (the arithmetic of conv_b3_kernel) ----------------------------------------------------------------------------------
+    // ---- epilogue (the f32 rule of conv_epilogue.hpp; one out_scale value per lane and channel block) -------------------------------------
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int n = n0 + (wn * NB + nb) * 32 + li;
@@ -374,11 +375,8 @@ __global__ __launch_bounds__((NCW + NPW) * 64, 1) void conv_b3_s2fir_kernel(floa
                 const int oy = oy0 + 2 * (wm * RB + rb) + (m >> 4), ox = ox0 + (m & 15);
                 if (oy >= p.OH || ox >= p.OW) continue;
                 const int64_t off = (((int64_t)pb * p.YH + oy) * p.YW + ox) * p.Cout + n;
-                float v = mul_rn(acc[rb][nb][e], p.gain);
-                if ((MODE == 1 || MOD) && out_scale) v = mul_rn(v, osv);
-                v = mul_then_add(v, 1.0f, bv);
-                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                if (resid) v = (v + resid[off]) * p.resid_gain;
+                float v = epi_head_val(acc[rb][nb][e], p, (MODE == 1 || MOD) && out_scale, osv, bv);
+                if (resid) v = epi_resid(v, resid[off], p);
                 y[off] = v;
             }
     }

@@ -27,6 +27,7 @@
 //  against the packed build: conv_igemm_multi 44.84 / 44.92 -> 45.00 / 44.98 ms, 0.3 % SLOWER; profiles/unpack_f32_family_ab.txt,
 //  unpack_f32_isa_counts.txt)
 #include "b3.hpp"
+#include "conv_epilogue.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -268,9 +269,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restric
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int q = aa * 32 + 8 * (e >> 2) + (e & 3);               // + 4 lh
-                    float v = mul_rn(acc[ph][aa][e], p.gain);
-                    if (out_scale) v = mul_rn(v, os);
-                    wl[((q + 4 * lh) ^ lh) * 32 + li] = v;
+                    wl[((q + 4 * lh) ^ lh) * 32 + li] = epi_scale_val(acc[ph][aa][e], p, out_scale != nullptr, os);
                 }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -300,9 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_tphase_kernel(float* __restric
             for (int e = 0; e < 16; ++e) {
                 const int ry = aa * 2 + (e >> 3), cx = (e & 3) + 8 * ((e >> 2) & 1);      // + 4 lh columns (lane_off)
                 if (!full && (qy0 + ry >= a.oh[ph] || qx0 + cx + 4 * lh >= a.ow[ph])) continue;
-                float v = mul_rn(acc[ph][aa][e], p.gain);
-                if (out_scale) v = mul_rn(v, os);
-                yb[lane_off + (unsigned)ry * rowstep + (unsigned)cx * colstep] = v;
+                yb[lane_off + (unsigned)ry * rowstep + (unsigned)cx * colstep] = epi_scale_val(acc[ph][aa][e], p, out_scale != nullptr, os);
             }
     }
 }

@@ -24,6 +24,7 @@
 //  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
+#include "conv_epilogue.hpp"
 #ifndef WINO_ABL
 #define WINO_ABL 0
 #endif
@@ -131,16 +132,13 @@ __device__ __forceinline__ void wino_finish4(float* __restrict__ y, const float*
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float o2 = px == 0 ? (mm[0][e] + mm[1][e]) + mm[2][e] : (mm[1][e] - mm[2][e]) - mm[3][e];
-                float t = mul_rn(o2, p.gain);
-                if (out_scale) t = mul_rn(t, osv[e]);
-                t = mul_then_add(t, 1.0f, bv[e]);
-                if (p.act) t = (t > 0.f ? t : t * p.alpha) * p.act_gain;
-                v[e] = t;
+                v[e] = epi_head_val(o2, p, out_scale != nullptr, osv[e], bv[e]);
             }
             if (resid) {
                 const float4 r4 = *reinterpret_cast<const float4*>(resid + yi);
-                v[0] = (v[0] + r4.x) * p.resid_gain; v[1] = (v[1] + r4.y) * p.resid_gain;
-                v[2] = (v[2] + r4.z) * p.resid_gain; v[3] = (v[3] + r4.w) * p.resid_gain;
+                const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = epi_resid(v[e], r[e], p);
             }
             if (p.accumulate) {
                 const float4 o4 = *reinterpret_cast<const float4*>(y + yi);
@@ -158,13 +156,10 @@ __device__ __forceinline__ void wino_finish4(float* __restrict__ y, const float*
         const float bvv = bias ? bias[n + e] : 0.f;
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-            float v = mul_rn(o2[px], p.gain);
-            if (out_scale) v = mul_rn(v, os);
-            v = mul_then_add(v, 1.0f, bvv);
-            if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
+            float v = epi_head_val(o2[px], p, out_scale != nullptr, os, bvv);
             const int64_t yi = opix + (int64_t)px * p.Cout + n + e;
-            if (resid) v = (v + resid[yi]) * p.resid_gain;
-            if (p.accumulate) y[yi] += v; else y[yi] = v;
+            if (resid) v = epi_resid(v, resid[yi], p);
+            epi_store(y, yi, v, p.accumulate);
         }
     }
 }
@@ -172,56 +167,9 @@ __device__ __forceinline__ bool wino_vec_ok(const float* y, const float* resid, 
     return (Cout & 3) == 0 && (((uintptr_t)y | (uintptr_t)resid | (uintptr_t)out_scale | (uintptr_t)bias) & 15) == 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Branch-free tails for the epilogue configurations the training step actually launches (round 5).  wino_finish4 tests five run-time
-// flags per channel quad (out_scale / bias / act / resid / accumulate): uniform branches, but each one ends a basic block, so its
-// loads are waited for one by one and nothing is packed -- ~600 of a wave's ~1550 vector instructions per 8-chunk tile, executed
-// with the matrix pipe idle.  Here the configuration is a template parameter chosen by ONE uniform switch per
-// half tile, a thread finishes its 8 channels x 2 pixels in straight-line code on 4-wide vectors (v_pk_add / v_pk_mul; no
-// contraction: the op order and roundings are wino_finish4's, the results bitwise equal), the leaky-ReLU is max(t, alpha t)
-// (equal to the select for 0 <= alpha <= 1, the only slopes admitted), and the four stores take 32-bit buffer offsets.
-//   OS: per-(sample, channel) output scale   BA: bias + leaky-ReLU * act_gain   RS: (v + resid) * resid_gain
-// ---------------------------------------------------------------------------------------------------------------
+// epilogue configurations with a branch-free tail (conv_epilogue.hpp::wino_finish_fast); EPI_GENERIC = wino_finish4
 enum { EPI_GENERIC = 0, EPI_PLAIN = 1, EPI_OS = 2, EPI_BA = 3, EPI_OS_BA = 4, EPI_OS_BA_RS = 5 };
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-template <bool OS, bool BA, bool RS>
-__device__ __forceinline__ void wino_finish_fast(__amdgpu_buffer_rsrc_t ry, unsigned yoff, unsigned px_step, const float* __restrict__ resid,
-                                                 const float* __restrict__ os_p, const float* __restrict__ bias_p,
-                                                 const float* __restrict__ ex, bool two, float gain, float alpha, float act_gain,
-                                                 float resid_gain) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        if (g == 1 && !two) break;
-        const v4f m0 = *reinterpret_cast<const v4f*>(ex + g * 4 + 0 * WP * XROW);
-        const v4f m1 = *reinterpret_cast<const v4f*>(ex + g * 4 + 1 * WP * XROW);
-        const v4f m2 = *reinterpret_cast<const v4f*>(ex + g * 4 + 2 * WP * XROW);
-        const v4f m3 = *reinterpret_cast<const v4f*>(ex + g * 4 + 3 * WP * XROW);
-        v4f osv, bv, r0, r1;
-        if (OS) osv = *reinterpret_cast<const v4f*>(os_p + g * 4);
-        if (BA) bv = *reinterpret_cast<const v4f*>(bias_p + g * 4);
-        if (RS) {
-            r0 = *reinterpret_cast<const v4f*>(resid + (yoff >> 2) + g * 4);
-            r1 = *reinterpret_cast<const v4f*>(resid + ((yoff + px_step) >> 2) + g * 4);
-        }
-        v4f t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3;
-        t0 = t0 * gain; t1 = t1 * gain;
-        if (OS) { t0 = t0 * osv; t1 = t1 * osv; }
-        if (BA) {
-            t0 = t0 + bv; t1 = t1 + bv;
-            const v4f a0 = t0 * alpha, a1 = t1 * alpha;
-            t0 = __builtin_elementwise_max(t0, a0) * act_gain;
-            t1 = __builtin_elementwise_max(t1, a1) * act_gain;
-        }
-        if (RS) { t0 = (t0 + r0) * resid_gain; t1 = (t1 + r1) * resid_gain; }
-        // (no SGPR offset on the stores: conv_b3_s2fir.hip records the data hazard of the `soffset` form on this part)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, t0), ry,
-                                               (int)(yoff + g * 16), 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, t1), ry,
-                                               (int)(yoff + px_step + g * 16), 0, 0);
-    }
-}
+constexpr int EXS = WP * XROW;     // floats between two components in the exchange buffer
 
 template <bool SCALE, bool REFLECT, int NH>
 __global__ __launch_bounds__(256 * NH, NH == 1 ? 3 : 1) void conv_b3_wino_kernel(float* __restrict__ y, const float* __restrict__ x,
@@ -492,11 +440,11 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 3 : 1) void conv_b3_wino_kernel
                 const float* bp = bias + n;
                 const bool two = n + 4 < p.Cout;
                 switch (epi) {
-                    case EPI_PLAIN: wino_finish_fast<false, false, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_OS: wino_finish_fast<true, false, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_BA: wino_finish_fast<false, true, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_OS_BA: wino_finish_fast<true, true, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    default: wino_finish_fast<true, true, true>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_PLAIN: wino_finish_fast<false, false, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_OS: wino_finish_fast<true, false, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_BA: wino_finish_fast<false, true, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_OS_BA: wino_finish_fast<true, true, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    default: wino_finish_fast<true, true, true, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
                 }
             }
         } else if (row_live) {
@@ -859,11 +807,11 @@ __global__ __launch_bounds__(512, 1) void conv_b3_wino2d_kernel(float* __restric
                 const float* bp = bias + n;
                 const bool two = n + 4 < p.Cout;
                 switch (epi) {                           // uniform
-                    case EPI_PLAIN: wino_finish_fast<false, false, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_OS: wino_finish_fast<true, false, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_BA: wino_finish_fast<false, true, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    case EPI_OS_BA: wino_finish_fast<true, true, false>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
-                    default: wino_finish_fast<true, true, true>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_PLAIN: wino_finish_fast<false, false, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_OS: wino_finish_fast<true, false, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_BA: wino_finish_fast<false, true, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    case EPI_OS_BA: wino_finish_fast<true, true, false, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
+                    default: wino_finish_fast<true, true, true, EXS>(ry, yoff, pxs, resid, osp, bp, ex, two, p.gain, p.alpha, p.act_gain, p.resid_gain); break;
                 }
             }
         } else {

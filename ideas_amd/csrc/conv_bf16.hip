@@ -28,11 +28,10 @@
 //       half-wave hit 32 different bank pairs;
 //     * split-K (XCD-banded, common.hpp: splitk_xcd_map) with f32 atomics into the (flat-bucket) f32 gradient; for modulated convs every split lies
 //       inside one image and the per-sample scales d[b,o] * s[b,ci] are applied to the accumulator in the epilogue.
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 #include <type_traits>
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -44,8 +43,6 @@ namespace {
 
 constexpr int KB = 32;          // bf16 K depth of one pipeline step (two MFMA K-slices)
 constexpr int ROW = 64;         // bytes per LDS row of the forward kernel
-constexpr unsigned RSRC = 0x00020000u;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 __device__ __forceinline__ uint4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
@@ -152,35 +149,9 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N <= 63, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-// The wait in front of a K-step's raw barrier: this wave's DMA pieces of the step have landed (counted vmcnt) AND its LDS reads of
-// the previous step have returned.  The second half matters: hipcc floats `s_barrier` (and a bare vmcnt wait) up over the previous
-// step's last MFMAs and over the `s_waitcnt lgkmcnt` in front of them, so a wave passed the barrier with ds_reads of stage t-1 still
-// queued -- and behind the barrier the other waves' DMA overwrites exactly that stage.  Alone the reads always won that race; next
-// to a kernel that keeps the LDS busy (the f32 split weight gradient on the side stream) the image kernel returned a few output
-// channels off by one K-step in 20 % of its launches (tools/probes/img_vs_b3wgrad.py; cdna_hip_programming.md: "raw s_barrier +
-// lgkmcnt(0)").
-template <int N> __device__ __forceinline__ void wait_step() {
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
+// (wait_step<N>, the wait in front of a K-step's raw barrier, is in conv_epilogue.hpp)
 
-// Register-only widening of the epilogue stores.  In the accumulator layout lane (li, lh) holds, per 32-channel block, the four
-// channel quads 8g + 4lh .. +3 (g = 0..3) of pixel li: 8-byte stores, 64 pieces per instruction.  v_permlane32_swap exchanges
-// lanes li and li + 32 (the two halves of the SAME pixel): swapping quad g of the upper half with quad g + 2 of the lower half
-// leaves lane (li, 0) with channels 0-15 and lane (li, 1) with channels 16-31 of the block -- two 16-byte stores per lane, 32
-// contiguous bytes, half the store instructions, no LDS.  out[c] = channels 8 (c + 2 lh) .. + 7 of the block.  With the stores compiled
-// out the 128-channel image kernel runs 1030 instead of 750 TFLOP/s at 256x256; this form recovers 820 (Dreal.1.conv1 710 -> 780,
-// E.2.conv1 575 -> 840).  (The tile through LDS as whole pixel rows, 128-byte lines per pixel, was the same speed.)
-__device__ __forceinline__ void quad_exchange(const uint2 (&q)[4], uint4 (&out)[2]) {
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const auto rx = __builtin_amdgcn_permlane32_swap(q[g].x, q[g + 2].x, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(q[g].y, q[g + 2].y, false, false);
-        out[g] = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-    }
-}
-
-template <int WM, int WN, int MT, int NT, int NST, bool PERIMG, bool REFLECT>
+template <int WM, int WN, int MT, int NT, int NST, bool PERIMG, bool REFLECT, bool BIAS = true>
 __device__ __forceinline__ void conv_bf16_body(bf16_t* __restrict__ y, const bf16_t* __restrict__ x, const void* __restrict__ wpack,
                                                const float* __restrict__ out_scale, const float* __restrict__ bias,
                                                const bf16_t* __restrict__ resid, const ideas_conv_params& p, int tile_m, int tile_n,
@@ -208,8 +179,8 @@ __device__ __forceinline__ void conv_bf16_body(bf16_t* __restrict__ y, const bf1
     const int64_t mend = PERIMG ? (int64_t)(img + 1) * OHW : M;     // first point this tile must not touch
     const int K = p.TY * p.TX * p.Cin;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, (int)w_bytes, (int)RSRC);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, (int)w_bytes, (int)RSRC_FLAGS);
     const unsigned w_img = PERIMG ? (unsigned)img * (unsigned)K * (unsigned)p.Cout * 2u : 0u;   // this image's pack
     const unsigned w_end = w_img + (unsigned)K * (unsigned)p.Cout * 2u;
 
@@ -330,68 +301,13 @@ __device__ __forceinline__ void conv_bf16_body(bf16_t* __restrict__ y, const bf1
     // ---- epilogue: lane = pixel li of block a; registers 4g..4g+3 = channels 8g + 4lh .. +3 of block b --------------------
     int64_t* row_off = reinterpret_cast<int64_t*>(smem);
     int* row_b = reinterpret_cast<int*>(smem + 8 * BM);
-    if (t < BM) {
-        const int64_t m = m0 + t;
-        int64_t off = -1;
-        int b = 0;
-        if (m < mend) {
-            const int ox = (int)(m % p.OW);
-            const int64_t q = m / p.OW;
-            const int oy = (int)(q % p.OH);
-            b = (int)(q / p.OH);
-            off = (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout;
-        }
-        row_off[t] = off;
-        row_b[t] = b;
-    }
+    epi_row_table(row_off, row_b, t, BM, m0, mend, p);
     __syncthreads();
-    const bool wide = (p.Cout & 7) == 0 && (((uintptr_t)y) & 15) == 0;      // 16-byte stores after a lane exchange (quad_exchange)
-#pragma unroll
-    for (int a = 0; a < MT; ++a) {
+    bf16_store_tile<true, BIAS>(y, resid, out_scale, bias, p, acc, [&](int a, int64_t& off, int& bimg) {
         const int row = (wm * MT + a) * 32 + li;
-        const int64_t off = row_off[row];
-        const int bimg = row_b[row];
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            uint2 q[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                q[g] = make_uint2(0u, 0u);
-                const int n = n0 + (wn * NT + b) * 32 + 8 * g + 4 * lh;
-                if (off < 0 || n >= p.Cout) continue;           // Cout % 4 == 0
-                float v[4];
-                const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 os = out_scale ? *reinterpret_cast<const float4*>(out_scale + (int64_t)bimg * p.Cout + n)
-                                            : make_float4(1.f, 1.f, 1.f, 1.f);
-                const float bvv[4] = {bv.x, bv.y, bv.z, bv.w}, osv[4] = {os.x, os.y, os.z, os.w};
-                uint2 rr = make_uint2(0u, 0u);
-                if (resid) rr = *reinterpret_cast<const uint2*>(resid + off + n);
-                const float rv[4] = {ideas_bf_lo(rr.x), ideas_bf_hi(rr.x), ideas_bf_lo(rr.y), ideas_bf_hi(rr.y)};
-                uint2 prev = make_uint2(0u, 0u);
-                if (p.accumulate) prev = *reinterpret_cast<const uint2*>(y + off + n);
-                const float pv[4] = {ideas_bf_lo(prev.x), ideas_bf_hi(prev.x), ideas_bf_lo(prev.y), ideas_bf_hi(prev.y)};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float u = acc[a][b][4 * g + j] * p.gain * osv[j] + bvv[j];
-                    if (p.act) u = (u > 0.f ? u : u * p.alpha) * p.act_gain;
-                    if (resid) u = (u + rv[j]) * p.resid_gain;
-                    if (p.accumulate) u += pv[j];
-                    v[j] = u;
-                }
-                q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
-                if (!wide) *reinterpret_cast<uint2*>(y + off + n) = q[g];
-            }
-            if (wide) {                                      // (block-uniform; every lane takes part in the exchange)
-                uint4 ch[2];
-                quad_exchange(q, ch);
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int n = n0 + (wn * NT + b) * 32 + 8 * (c + 2 * lh);
-                    if (off >= 0 && n < p.Cout) *reinterpret_cast<uint4*>(y + off + n) = ch[c];
-                }
-            }
-        }
-    }
+        off = row_off[row];
+        bimg = row_b[row];
+    }, n0, wn, lh);
 }
 
 template <int WM, int WN, int MT, int NT, int NST, bool PERIMG, bool REFLECT>
@@ -424,7 +340,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_multi_kernel(bf16_t* _
     const int bid = blockIdx.x;
     const int which = (bid >= a.off[1] && a.n > 1) + (bid >= a.off[2] && a.n > 2) + (bid >= a.off[3] && a.n > 3);
     const int swz = xcd_swizzle(bid - a.off[which], a.off[which + 1] - a.off[which]);
-    conv_bf16_body<WM, WN, MT, NT, 3, PERIMG, false>(y, x, a.w[which], out_scale, nullptr, nullptr, a.p[which], swz / a.tiles_n,
+    conv_bf16_body<WM, WN, MT, NT, 3, PERIMG, false, false>(y, x, a.w[which], out_scale, nullptr, nullptr, a.p[which], swz / a.tiles_n,
                                                      swz % a.tiles_n, a.tpi[which], x_bytes, a.w_bytes[which]);
 }
 
@@ -509,8 +425,8 @@ __global__ __launch_bounds__(512, 4) void conv_bf16_img_kernel(bf16_t* __restric
     const int K = 9 * p.Cin;
     const bool flip = p.dy < 0;                      // input gradient: tap ty reads row oy + 1 - ty
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, (int)w_bytes, (int)RSRC);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, (int)w_bytes, (int)RSRC_FLAGS);
     const unsigned w_img = PERIMG ? (unsigned)img * (unsigned)K * (unsigned)p.Cout * 2u : 0u;
     const unsigned w_end = w_img + (unsigned)K * (unsigned)p.Cout * 2u;
 
@@ -633,51 +549,10 @@ __global__ __launch_bounds__(512, 4) void conv_bf16_img_kernel(bf16_t* __restric
         row_off[t] = (((int64_t)img * p.YH + y0 + prow) * p.YW + x0 + pcol) * p.Cout;
     }
     __syncthreads();
-    const bool wide = (p.Cout & 7) == 0 && (((uintptr_t)y) & 15) == 0;      // 16-byte stores after a lane exchange (quad_exchange)
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const int64_t off = row_off[wm * 64 + a * 32 + li];
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            uint2 q[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                q[g] = make_uint2(0u, 0u);
-                const int n = n0 + (wn * NT + b) * 32 + 8 * g + 4 * lh;
-                if (n >= p.Cout) continue;           // Cout % 4 == 0
-                float v[4];
-                const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 os = out_scale ? *reinterpret_cast<const float4*>(out_scale + (int64_t)img * p.Cout + n)
-                                            : make_float4(1.f, 1.f, 1.f, 1.f);
-                const float bvv[4] = {bv.x, bv.y, bv.z, bv.w}, osv[4] = {os.x, os.y, os.z, os.w};
-                uint2 rr = make_uint2(0u, 0u);
-                if (resid) rr = *reinterpret_cast<const uint2*>(resid + off + n);
-                const float rv[4] = {ideas_bf_lo(rr.x), ideas_bf_hi(rr.x), ideas_bf_lo(rr.y), ideas_bf_hi(rr.y)};
-                uint2 prev = make_uint2(0u, 0u);
-                if (p.accumulate) prev = *reinterpret_cast<const uint2*>(y + off + n);
-                const float pv[4] = {ideas_bf_lo(prev.x), ideas_bf_hi(prev.x), ideas_bf_lo(prev.y), ideas_bf_hi(prev.y)};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float u = acc[a][b][4 * g + j] * p.gain * osv[j] + bvv[j];
-                    if (p.act) u = (u > 0.f ? u : u * p.alpha) * p.act_gain;
-                    if (resid) u = (u + rv[j]) * p.resid_gain;
-                    if (p.accumulate) u += pv[j];
-                    v[j] = u;
-                }
-                q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
-                if (!wide) *reinterpret_cast<uint2*>(y + off + n) = q[g];
-            }
-            if (wide) {                                      // (block-uniform; every lane takes part in the exchange)
-                uint4 ch[2];
-                quad_exchange(q, ch);
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int n = n0 + (wn * NT + b) * 32 + 8 * (c + 2 * lh);
-                    if (n < p.Cout) *reinterpret_cast<uint4*>(y + off + n) = ch[c];
-                }
-            }
-        }
-    }
+    bf16_store_tile<false, true>(y, resid, out_scale, bias, p, acc, [&](int a, int64_t& off, int& bimg) {     // (no masked rows in a patch)
+        off = row_off[wm * 64 + a * 32 + li];
+        bimg = img;
+    }, n0, wn, lh);
 }
 
 static int bf16_img_tp(const ideas_conv_params* p) {      // patch width of the image kernel for this geometry, 0 = not its geometry
@@ -786,8 +661,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_wgrad_kernel(float* __
     const int pend = pbeg + pix_per_split < plim ? pbeg + pix_per_split : plim;
     if (pbeg >= pend) return;
 
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gy, 0, (int)gy_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC);
+    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gy, 0, (int)gy_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC_FLAGS);
 
     // ---- this lane's DMA slots: piece q = wave + 4 j; LDS slot = 64 (q - first piece of its operand) + lane --------------
     int s_pix[PER];                    // pixel row (0..31) within the step
@@ -1183,8 +1058,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_wgrad3_kernel(float* __restr
     const int ob = oa + rows_per_part < p.OH ? oa + rows_per_part : p.OH;
     if (oa >= ob) return;
 
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gy, 0, (int)gy_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC);
+    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gy, 0, (int)gy_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC_FLAGS);
 
     // ---- DMA slots of a wave per step: G piece `swave` (8 pixels), X piece `swave`, X piece 4 (every wave: same bytes) --------------
     // lane l fills position l & 7 of LDS pixel 8 q + (l >> 3), which must hold channel chunk (l & 7) ^ (((pixel >> 1) & 1) << 2)

@@ -16,33 +16,15 @@
 //     out-of-range offset are dropped -- and every store IS issued (no branch around it), which is what makes the count a constant.
 // MFMA roles, K order (ascending 16-channel slices) and the epilogue expression are conv_bf16_body's: the results are BITWISE the
 // generic kernel's (tests/test_ops_gpu.py).
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef unsigned short bf16_t;
 
 namespace {
-
-constexpr unsigned RSRC = 0x00020000u;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N> __device__ __forceinline__ void wait_step() {       // (conv_bf16.hip: the LDS reads must have returned as well)
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-// lanes li / li + 32 hold channel quads 8g + 4lh of one pixel: after the swap lane (li, 0) has channels 0-15, (li, 1) 16-31 (conv_bf16.hip)
-__device__ __forceinline__ void quad_exchange(const uint2 (&q)[4], uint4 (&out)[2]) {
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const auto rx = __builtin_amdgcn_permlane32_swap(q[g].x, q[g + 2].x, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(q[g].y, q[g + 2].y, false, false);
-        out[g] = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-    }
-}
 
 // KS = Cin / 32 (1, 2, 4); a block = 2 x 2 waves over 128 pixels x (64 NT) channels per pass, NP passes with their weights resident
 template <int KS, int NT, int NP>
@@ -67,11 +49,11 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_pw_kernel(bf16_t* __restrict
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
     const unsigned x_bytes = M * (unsigned)RB, y_bytes = M * (unsigned)p.Cout * 2u;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, CIN * p.Cout * 2, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, (int)y_bytes, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)resid, 0, resid ? (int)y_bytes : 0, (int)RSRC);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)bias, 0, bias ? p.Cout * 4 : 0, (int)RSRC);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)x_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, CIN * p.Cout * 2, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, (int)y_bytes, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)resid, 0, resid ? (int)y_bytes : 0, (int)RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)bias, 0, bias ? p.Cout * 4 : 0, (int)RSRC_FLAGS);
 
     // DMA: piece q = wave + 4 j holds rows q RPP .. + RPP - 1; lane l fills LDS slot l = (row l / CR, position l % CR), which must hold
     // chunk (l % CR) ^ swizzle(row) of that row
@@ -170,12 +152,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_pw_kernel(bf16_t* __restrict
                         const float rv[4] = {ideas_bf_lo(rq.x), ideas_bf_hi(rq.x), ideas_bf_lo(rq.y), ideas_bf_hi(rq.y)};
                         float v[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float u = mul_then_add(acc[a][b][4 * g + j], p.gain, bvv[j]);   // (= the generic kernel's fma(acc * gain, out_scale = 1, bias))
-                            if (p.act) u = (u > 0.f ? u : u * p.alpha) * p.act_gain;
-                            if (resid) u = (u + rv[j]) * p.resid_gain;
-                            v[j] = u;
-                        }
+                        for (int j = 0; j < 4; ++j)     // the generic kernel's rule with out_scale = 1 and no accumulation
+                            v[j] = epi_bf16(acc[a][b][4 * g + j], p, 1.f, bvv[j], resid != nullptr, rv[j], false, 0.f);
                         q[g] = make_uint2(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]));
                     }
                     uint4 ch[2];

@@ -4,21 +4,12 @@
 // to_rgb's input gradient (3 channels in) and Ex's last layer (N channels out).  They are HBM-bound (a few
 // MACs per byte), so a thread per (pixel, output channel) with coalesced stores is enough; the MFMA tile
 // would be >90 % padding.  It doubles as the on-device cross-check for the MFMA kernel in tests.
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 
 namespace {
 
-// element access for the two activation dtypes (float, or bf16 stored as unsigned short): f32 arithmetic either way
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float ldv(const float* p) { return *p; }
-__device__ __forceinline__ float ldv(const bf16_t* p) { return __builtin_bit_cast(float, (unsigned)(*p) << 16); }
-__device__ __forceinline__ void stv(float* p, float v) { *p = v; }
-__device__ __forceinline__ void stv(bf16_t* p, float v) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 t = {v, 0.f};
-    *p = (bf16_t)(__builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2)) & 0xffffu);   // RNE
-}
+// the two activation dtypes (float, or bf16 stored as unsigned short) through common.hpp's ld1 / st1: f32 arithmetic either way
+typedef ideas_bf16 bf16_t;
 
 __device__ __forceinline__ bool in_coord(int& i, int n, int reflect) {
     if (reflect) { i = reflect_coord(i, n); return true; }
@@ -51,20 +42,17 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(T* __restrict__ y, con
                 const float* wp = wr + (ty * p.TX + tx) * p.Cin;
                 if (in_scale) {
                     const float* sp = in_scale + (int64_t)b * p.Cin;
-                    for (int ci = 0; ci < p.Cin; ++ci) acc = fmaf(ldv(xp + ci) * sp[ci], wp[ci], acc);
+                    for (int ci = 0; ci < p.Cin; ++ci) acc = fmaf(ld1(xp + ci) * sp[ci], wp[ci], acc);
                 } else {
-                    for (int ci = 0; ci < p.Cin; ++ci) acc = fmaf(ldv(xp + ci), wp[ci], acc);
+                    for (int ci = 0; ci < p.Cin; ++ci) acc = fmaf(ld1(xp + ci), wp[ci], acc);
                 }
             }
         }
-        float v = mul_rn(acc, p.gain);
-        if (out_scale) v = mul_rn(v, out_scale[(int64_t)b * p.Cout + o]);
-        v = mul_then_add(v, 1.0f, bias ? bias[o] : 0.f);
-        if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
+        float v = epi_scale(acc, p, out_scale, (int64_t)b * p.Cout + o);
+        v = epi_bias_act(v, p, bias ? bias[o] : 0.f);
         const int64_t yi = (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout + o;
-        if (resid) v = (v + ldv(resid + yi)) * p.resid_gain;
-        if (p.accumulate) v += ldv(y + yi);
-        stv(y + yi, v);
+        if (resid) v = epi_resid(v, ld1(resid + yi), p);
+        epi_store(y, yi, v, p.accumulate);
     }
 }
 
@@ -95,9 +83,9 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(float* __restrict__ g
             int iy = oy * p.sy + ty * p.dy + p.offy;
             int ix = ox * p.sx + tx * p.dx + p.offx;
             if (!in_coord(iy, p.IH, p.reflect) || !in_coord(ix, p.IW, p.reflect)) continue;
-            float xv = ldv(x + (((int64_t)b * p.IH + iy) * p.IW + ix) * p.Cin + ci);
+            float xv = ld1(x + (((int64_t)b * p.IH + iy) * p.IW + ix) * p.Cin + ci);
             if (in_scale) xv *= in_scale[(int64_t)b * p.Cin + ci];
-            float g = ldv(gy + (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout + o);
+            float g = ld1(gy + (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout + o);
             if (out_scale) g *= out_scale[(int64_t)b * p.Cout + o];
             acc = fmaf(g, xv, acc);
         }
@@ -115,6 +103,7 @@ __global__ __launch_bounds__(256) void pointwise_smallk_kernel(T* __restrict__ y
                                                                const T* __restrict__ resid, int64_t P, int Cin, int Cout,
                                                                float gain, int act, float alpha, float act_gain,
                                                                float resid_gain, int accumulate) {
+    const EpiScalars ep{gain, act, alpha, act_gain, resid_gain};
     const int groups = blockDim.x / Cout;            // pixel lanes per block
     const int o = threadIdx.x % Cout, grp = threadIdx.x / Cout;
     if (grp >= groups) return;
@@ -128,13 +117,11 @@ __global__ __launch_bounds__(256) void pointwise_smallk_kernel(T* __restrict__ y
         float acc = 0.f;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
-            if (k < Cin) acc = fmaf(ldv(xp + k), wr[k], acc);
-        float v = mul_then_add(acc, gain, bv);   // no FMA contraction: bitwise the unfused conv -> bias_act
-        if (act) v = (v > 0.f ? v : v * alpha) * act_gain;
+            if (k < Cin) acc = fmaf(ld1(xp + k), wr[k], acc);
+        float v = epi_head(acc, ep, bv);
         const int64_t yi = pp * Cout + o;
-        if (resid) v = (v + ldv(resid + yi)) * resid_gain;
-        if (accumulate) v += ldv(y + yi);
-        stv(y + yi, v);
+        if (resid) v = epi_resid(v, ld1(resid + yi), ep);
+        epi_store(y, yi, v, accumulate);
     }
 }
 
@@ -151,6 +138,7 @@ __global__ __launch_bounds__(256) void pointwise_smallk_vec_kernel(T* __restrict
                                                                    float gain, int act, float alpha, float act_gain,
                                                                    float resid_gain, int accumulate) {
     typedef typename Vec4Of<T>::type V;
+    const EpiScalars ep{gain, act, alpha, act_gain, resid_gain};
     const int C4 = Cout >> 2;
     const int groups = blockDim.x / C4;              // pixel lanes per block
     const int o4 = threadIdx.x % C4, grp = threadIdx.x / C4;
@@ -170,7 +158,7 @@ __global__ __launch_bounds__(256) void pointwise_smallk_vec_kernel(T* __restrict
         const T* xp = x + pp * Cin;
         float xs[KMAX];
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k) xs[k] = k < Cin ? ldv(xp + k) : 0.f;
+        for (int k = 0; k < KMAX; ++k) xs[k] = k < Cin ? ld1(xp + k) : 0.f;
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -178,14 +166,14 @@ __global__ __launch_bounds__(256) void pointwise_smallk_vec_kernel(T* __restrict
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
                 if (k < Cin) acc = fmaf(xs[k], wr[e][k], acc);
-            float t = mul_then_add(acc, gain, bv[e]);
-            if (act) t = (t > 0.f ? t : t * alpha) * act_gain;
-            v[e] = t;
+            v[e] = epi_head(acc, ep, bv[e]);
         }
         const int64_t yi = pp * C4 + o4;
         if (resid) {
             const float4 r4 = to_f4(rv[yi]);
-            v[0] = (v[0] + r4.x) * resid_gain; v[1] = (v[1] + r4.y) * resid_gain; v[2] = (v[2] + r4.z) * resid_gain; v[3] = (v[3] + r4.w) * resid_gain;
+            const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = epi_resid(v[e], r[e], ep);
         }
         if (accumulate) {
             const float4 a4 = to_f4(yv[yi]);
@@ -216,11 +204,11 @@ __global__ __launch_bounds__(256) void pointwise_small_wgrad_kernel(float* __res
 #pragma unroll
             for (int k = 0; k < SMALL; ++k) acc[k] = 0.f;
             for (int64_t pp = p0 + grp; pp < p1; pp += groups) {
-                const float a = WIDE_OUT ? ldv(gy + pp * Cout + c) : ldv(x + pp * Cin + c);
+                const float a = WIDE_OUT ? ld1(gy + pp * Cout + c) : ld1(x + pp * Cin + c);
                 const T* bp = WIDE_OUT ? x + pp * Cin : gy + pp * Cout;
 #pragma unroll
                 for (int k = 0; k < SMALL; ++k)
-                    if (k < small) acc[k] = fmaf(a, ldv(bp + k), acc[k]);
+                    if (k < small) acc[k] = fmaf(a, ld1(bp + k), acc[k]);
             }
 #pragma unroll
             for (int k = 0; k < SMALL; ++k)
@@ -266,6 +254,7 @@ __global__ __launch_bounds__(256) void pointwise_rowdot_kernel(T* __restrict__ y
                                                                int Cin, int Cout, int L, float gain, int act, float alpha,
                                                                float act_gain, float resid_gain, int accumulate) {
     constexpr int VEC = VecOf<T>::N;
+    const EpiScalars ep{gain, act, alpha, act_gain, resid_gain};
     const int lane = threadIdx.x & 63;
     const int sub = lane & (L - 1), grp = lane / L, G = 64 / L;        // lane within its pixel group, group within the wave
     float wr[NS][IT][VEC];
@@ -300,12 +289,10 @@ __global__ __launch_bounds__(256) void pointwise_rowdot_kernel(T* __restrict__ y
             float a = acc[0];
 #pragma unroll
             for (int o = 1; o < NS; ++o) a = sub == o ? acc[o] : a;
-            float v = mul_then_add(a, gain, bias ? bias[sub] : 0.f);
-            if (act) v = (v > 0.f ? v : v * alpha) * act_gain;
+            float v = epi_head(a, ep, bias ? bias[sub] : 0.f);
             const int64_t yi = pp * Cout + sub;
-            if (resid) v = (v + ldv(resid + yi)) * resid_gain;
-            if (accumulate) v += ldv(y + yi);
-            stv(y + yi, v);
+            if (resid) v = epi_resid(v, ld1(resid + yi), ep);
+            epi_store(y, yi, v, accumulate);
         }
     }
 }
@@ -333,7 +320,7 @@ __global__ __launch_bounds__(256) void pointwise_wgrad_vec_kernel(float* __restr
     for (int64_t pp = p0 + wv * G + grp; pp < p1; pp += 4 * G) {
         float sv[NS];
 #pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) sv[s_] = s_ < Cs ? ldv(S + pp * Cs + s_) : 0.f;
+        for (int s_ = 0; s_ < NS; ++s_) sv[s_] = s_ < Cs ? ld1(S + pp * Cs + s_) : 0.f;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             float f[VEC];

@@ -23,22 +23,13 @@
 // Workgroup -> tile mapping is XCD-aware: hardware round-robins consecutive workgroup ids over the 8 XCDs,
 // so ids are remapped to give each XCD (= each private L2) one contiguous band of M tiles with all its N
 // tiles; 3x3 halos and the N-tile re-reads of the same activations then hit that XCD's L2.
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
 constexpr int BK = 16;    // K (or pixel) depth of one pipeline step
 constexpr int LDK = 20;   // padded LDS row length (floats) of the K-contiguous tiles
-
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-// component-wise select: a ternary on the float4 aggregates becomes a select between two ADDRESSES, which forces
-// the staging registers into scratch memory (seen in the ISA as scratch_store + vmcnt(0) after every load)
-__device__ __forceinline__ float4 keep4(bool ok, float4 v) {
-    return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
-}
 
 // =====================================================================================================
 // forward family
@@ -232,20 +223,7 @@ __global__ __launch_bounds__(256, SCALE ? 3 : 4) void conv_igemm_kernel(float* _
     // ---- epilogue: row table (output offset, batch index) in LDS, then masked coalesced stores --------
     int64_t* row_off = reinterpret_cast<int64_t*>(smem);
     int* row_b = reinterpret_cast<int*>(smem + 2 * BM);
-    if (t < BM) {
-        const int64_t m = m0 + t;
-        int64_t off = -1;
-        int b = 0;
-        if (m < M) {
-            const int ox = (int)(m % p.OW);
-            const int64_t q = m / p.OW;
-            const int oy = (int)(q % p.OH);
-            b = (int)(q / p.OH);
-            off = (((int64_t)b * p.YH + (oy * p.osy + p.ooy)) * p.YW + (ox * p.osx + p.oox)) * p.Cout;
-        }
-        row_off[t] = off;
-        row_b[t] = b;
-    }
+    epi_row_table(row_off, row_b, t, BM, m0, M, p);
     __syncthreads();
 #pragma unroll
     for (int b = 0; b < NT; ++b) {
@@ -259,12 +237,9 @@ __global__ __launch_bounds__(256, SCALE ? 3 : 4) void conv_igemm_kernel(float* _
                 const int row = (wm * MT + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 const int64_t off = row_off[row];
                 if (off < 0) continue;
-                float v = mul_rn(acc[a][b][r], p.gain);      // separate roundings (no FMA contraction): the fused
-                if (out_scale) v = mul_rn(v, out_scale[(int64_t)row_b[row] * p.Cout + n]);
-                v = mul_then_add(v, 1.0f, bv);               // epilogue is bitwise conv -> fused_bias_act
-                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
-                if (resid) v = (v + resid[off + n]) * p.resid_gain;
-                if (p.accumulate) y[off + n] += v; else y[off + n] = v;
+                float v = epi_head(acc[a][b][r], p, out_scale, (int64_t)row_b[row] * p.Cout + n, bv);
+                if (resid) v = epi_resid(v, resid[off + n], p);
+                epi_store(y, off + n, v, p.accumulate);
             }
         }
     }

@@ -19,10 +19,8 @@
 // rows [32w, 32w+32) x 64 channels x 4 v = 8 accumulators of 32x32.  LDS rows are 8 floats with an XOR slot swizzle
 // ((row>>3)&1) instead of padding -> conflict-free ds_read_b128, 48 KB double-buffered.  Same pipeline as
 // conv_igemm: one basic block per K-step, loads of step t+2 issued while step t computes.
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -32,17 +30,7 @@ constexpr int WBK = 8;    // K depth per step
 
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 mulv4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 keepv4(bool ok, float4 v) {
-    return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
-}
 __device__ __forceinline__ int wino_swizzle(int row, int slot) { return (slot ^ ((row >> 3) & 1)) * 4; }
-
-__device__ __forceinline__ int xcd_swz(int bid, int nblk) {
-    const int q = nblk >> 3, rem = nblk & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
-}
 
 template <bool SCALE, bool REFLECT>
 __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(float* __restrict__ y, const float* __restrict__ x,
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(float* __restrict_
     const int H = p.IH, W = p.IW, W2 = W >> 1;
     const int64_t M = (int64_t)p.B * H * W2;
     const int K = 3 * p.Cin;
-    const int swz = xcd_swz(blockIdx.x, gridDim.x);
+    const int swz = xcd_swizzle(blockIdx.x, gridDim.x);
     const int tile_n = swz % tiles_n, tile_m = swz / tiles_n;
     const int64_t m0 = (int64_t)tile_m * WBM;
     const int n0 = tile_n * WBN;
@@ -127,9 +115,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(float* __restrict_
     };
     // the predicate of the B rows for the tile held in rb (kval belongs to the same gload)
     auto lstore = [&](int buf) {
-        float4 d0 = keepv4(okd[0], rd[0]), d1 = keepv4(okd[1], rd[1]), d2 = keepv4(okd[2], rd[2]), d3 = keepv4(okd[3], rd[3]);
+        float4 d0 = keep4(okd[0], rd[0]), d1 = keep4(okd[1], rd[1]), d2 = keep4(okd[2], rd[2]), d3 = keep4(okd[3], rd[3]);
         float4 v0 = sub4(d0, d2), v1 = add4(d1, d2), v2 = sub4(d2, d1), v3 = sub4(d1, d3);
-        if (SCALE) { v0 = mulv4(v0, rs); v1 = mulv4(v1, rs); v2 = mulv4(v2, rs); v3 = mulv4(v3, rs); }
+        if (SCALE) { v0 = mul4(v0, rs); v1 = mul4(v1, rs); v2 = mul4(v2, rs); v3 = mul4(v3, rs); }
         float* a = As + buf * A_FLOATS + ar * WBK + wino_swizzle(ar, akq);
         *reinterpret_cast<float4*>(a + 0 * WBM * WBK) = v0;
         *reinterpret_cast<float4*>(a + 1 * WBM * WBK) = v1;
@@ -137,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(float* __restrict_
         *reinterpret_cast<float4*>(a + 3 * WBM * WBK) = v3;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            *reinterpret_cast<float4*>(Bs + buf * B_FLOATS + b_dst[j]) = keepv4(b_ok[j] && kval, rb[j]);
+            *reinterpret_cast<float4*>(Bs + buf * B_FLOATS + b_dst[j]) = keep4(b_ok[j] && kval, rb[j]);
     };
 
     const int lane = t & 63, wave = t >> 6;
@@ -219,13 +207,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(float* __restrict_
             const float os = out_scale ? out_scale[(int64_t)row_b[row] * p.Cout + n] : 1.f;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                float v = mul_rn(o[e], p.gain);
-                if (out_scale) v = mul_rn(v, os);
-                v = mul_then_add(v, 1.0f, bvv);
-                if (p.act) v = (v > 0.f ? v : v * p.alpha) * p.act_gain;
+                float v = epi_head_val(o[e], p, out_scale != nullptr, os, bvv);
                 const int64_t yi = off + (int64_t)e * p.Cout + n;
-                if (resid) v = (v + resid[yi]) * p.resid_gain;
-                if (p.accumulate) y[yi] += v; else y[yi] = v;
+                if (resid) v = epi_resid(v, resid[yi], p);
+                epi_store(y, yi, v, p.accumulate);
             }
         }
     }
@@ -340,17 +325,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_wgrad_kernel(float* __res
     };
     auto lstore = [&](int buf) {
         if (g_active) {
-            float4 g0 = keepv4(okg, rg[0]), g1 = keepv4(okg, rg[1]);
-            if (SCALE) { g0 = mulv4(g0, rgs); g1 = mulv4(g1, rgs); }
+            float4 g0 = keep4(okg, rg[0]), g1 = keep4(okg, rg[1]);
+            if (SCALE) { g0 = mul4(g0, rgs); g1 = mul4(g1, rgs); }
             float* dst = Gs + buf * G_FLOATS + g_pr * LDM + g_oq * 4;
             *reinterpret_cast<float4*>(dst + 0 * GBK * LDM) = g0;
             *reinterpret_cast<float4*>(dst + 1 * GBK * LDM) = add4(g0, g1);
             *reinterpret_cast<float4*>(dst + 2 * GBK * LDM) = sub4(g0, g1);
             *reinterpret_cast<float4*>(dst + 3 * GBK * LDM) = make_float4(-g1.x, -g1.y, -g1.z, -g1.w);
         }
-        float4 d0 = keepv4(okx[0], rx[0]), d1 = keepv4(okx[1], rx[1]), d2 = keepv4(okx[2], rx[2]), d3 = keepv4(okx[3], rx[3]);
+        float4 d0 = keep4(okx[0], rx[0]), d1 = keep4(okx[1], rx[1]), d2 = keep4(okx[2], rx[2]), d3 = keep4(okx[3], rx[3]);
         float4 v0 = sub4(d0, d2), v1 = add4(d1, d2), v2 = sub4(d2, d1), v3 = sub4(d1, d3);
-        if (SCALE) { v0 = mulv4(v0, rxs); v1 = mulv4(v1, rxs); v2 = mulv4(v2, rxs); v3 = mulv4(v3, rxs); }
+        if (SCALE) { v0 = mul4(v0, rxs); v1 = mul4(v1, rxs); v2 = mul4(v2, rxs); v3 = mul4(v3, rxs); }
         float* dst = Xs + buf * X_FLOATS + x_pr * LDN + x_kq * 4;
         *reinterpret_cast<float4*>(dst + 0 * GBK * LDN) = v0;
         *reinterpret_cast<float4*>(dst + 1 * GBK * LDN) = v1;

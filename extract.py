@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""Get a hidden file back from container images (the receiver of IDEAS: 8-bit images -> E -> Ex -> bits -> payload).
+
+    python extract.py --ckpt CHECKPOINT [--sigma 1] --out FILE [--dump_bits F.npy] [--batch 32] IMAGES...
+
+``IMAGES`` are the files ``hide.py`` wrote, in order.  Exit status 0 and the payload in ``FILE`` when the length and the CRC32 of the
+frame hold; status 1 with a one-line message and no payload file when they do not.  ``--dump_bits`` saves the extracted packed bits
+(uint8 [n_images, capacity / 8]) whatever the check says.
+"""
+import argparse
+import sys
+
+import numpy as np
+import torch
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="extract a hidden payload from IDEAS container images")
+    parser.add_argument("--ckpt", type=str, required=True, help="the checkpoint hide.py used")
+    parser.add_argument("--sigma", type=int, default=1, help="bits per element of the secret tensor (1..8), as given to hide.py")
+    parser.add_argument("--out", type=str, required=True, help="where the payload is written")
+    parser.add_argument("--dump_bits", type=str, default=None, metavar="F.npy", help="also save the extracted packed bits")
+    parser.add_argument("--batch", type=int, default=32)
+    parser.add_argument("images", metavar="IMAGES", nargs="+")
+    opt = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        raise SystemExit("extract.py needs a GPU (ideas_amd has no CPU path)")
+    from PIL import Image
+    from ideas_amd import stego
+
+    device = torch.device("cuda")
+    models, args = stego.load_models(opt.ckpt, device)
+    cap = stego.capacity_bits(args, opt.sigma)
+    if cap % 8:
+        raise SystemExit(f"extract.py: the capacity of an image ({cap} bits) is not a whole number of bytes (needs image_size >= 64)")
+    size = int(args.image_size)
+    rows = []
+    for i0 in range(0, len(opt.images), opt.batch):
+        batch = []
+        for path in opt.images[i0:i0 + opt.batch]:
+            with Image.open(path) as img:
+                arr = np.asarray(img.convert("RGB"), dtype=np.uint8)
+            if arr.shape != (size, size, 3):
+                raise SystemExit(f"extract.py: {path} is {arr.shape[1]}x{arr.shape[0]}, the checkpoint's images are {size}x{size}")
+            batch.append(torch.from_numpy(arr.copy()))
+        bits, _ = stego.extract(models, args, torch.stack(batch).to(device), opt.sigma)
+        rows.append(bits.cpu())
+    rows = torch.cat(rows, 0)
+    if opt.dump_bits:
+        np.save(opt.dump_bits, rows.numpy())
+    try:
+        payload = stego.unframe(rows)
+    except stego.PayloadError as e:
+        print(f"extract.py: no payload recovered, the length / CRC check of the frame failed: {e}", file=sys.stderr)
+        return 1
+    with open(opt.out, "wb") as f:
+        f.write(payload)
+    print(f"recovered {len(payload)} bytes from {rows.shape[0]} image(s) -> {opt.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

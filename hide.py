@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Hide a file in synthesised images (the sender of IDEAS: payload bits -> secret tensor -> Gstru -> G -> 8-bit PNGs).
+
+    python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32]
+
+The payload is framed (4-byte length, CRC32, payload, random padding: ``ideas_amd.stego.frame``) into whole images of
+``N * (image_size / 16)^2 * sigma`` bits each and written as ``DIR/000000.png``, ``DIR/000001.png``, ...  ``extract.py`` with the same
+checkpoint and ``--sigma`` reads them back.  The same ``--seed`` gives the same files.
+"""
+import argparse
+import os
+
+import torch
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="hide a payload file in images synthesised by a trained IDEAS checkpoint")
+    parser.add_argument("--ckpt", type=str, required=True, help="checkpoint in the reference's format ({iter}.pt)")
+    parser.add_argument("--payload", type=str, required=True, help="the file to hide")
+    parser.add_argument("--out", type=str, required=True, help="directory for the PNG containers")
+    parser.add_argument("--sigma", type=int, default=1, help="bits per element of the secret tensor (1..8)")
+    parser.add_argument("--delta", type=float, default=0.5, help="jitter half-width as a fraction of a bin")
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--batch", type=int, default=32)
+    opt = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        raise SystemExit("hide.py needs a GPU (ideas_amd has no CPU path)")
+    from PIL import Image
+    from ideas_amd import stego
+    from ideas_amd.op import quantize_image
+
+    device = torch.device("cuda")
+    models, args = stego.load_models(opt.ckpt, device)
+    cap = stego.capacity_bits(args, opt.sigma)
+    if cap % 8:
+        raise SystemExit(f"hide.py: the capacity of an image ({cap} bits) is not a whole number of bytes (needs image_size >= 64)")
+    with open(opt.payload, "rb") as f:
+        payload = f.read()
+    rows = stego.frame(payload, cap // 8, torch.Generator().manual_seed(opt.seed))
+    gen = torch.Generator(device=device).manual_seed(opt.seed)
+    os.makedirs(opt.out, exist_ok=True)
+    print(f"capacity per image: {cap} bits ({cap // 8} bytes); payload {len(payload)} bytes -> {rows.shape[0]} image(s)")
+    for i0 in range(0, rows.shape[0], opt.batch):
+        bits = rows[i0:i0 + opt.batch].to(device)
+        images, _ = stego.hide(models, args, bits, opt.sigma, opt.delta, generator=gen)
+        u8, _ = quantize_image(images, dequantize=False)
+        for k, img in enumerate(u8.cpu().numpy()):
+            Image.fromarray(img).save(os.path.join(opt.out, f"{i0 + k:06d}.png"))
+    print(f"wrote {rows.shape[0]} image(s) to {opt.out}")
+
+
+if __name__ == "__main__":
+    main()

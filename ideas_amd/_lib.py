@@ -154,6 +154,9 @@ _PROTOS = {
     "ideas_pool3x3_fwd": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
     "ideas_global_avg_pool": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_feature_stats_accum": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "ideas_bits_to_tensor": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "ideas_tensor_to_bits": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ideas_image_f32_to_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

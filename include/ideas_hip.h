@@ -543,6 +543,36 @@ int ideas_global_avg_pool(float* out, const void* x, int B, int C, int H, int W,
 int ideas_feature_stats_accum(double* sum, double* gram, const float* x, int N, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Steganography codec (utils.py:74-97 on packed bits) and the container's trip through an 8-bit image file, csrc/stego.hip.
+ * Packed bits: one row of nbytes = ceil(L * sigma / 8) bytes per image.  Message bit j of image b is
+ *     (row[b][j >> 3] >> (7 - (j & 7))) & 1
+ * and element l takes message bits [l * sigma, (l + 1) * sigma), most significant first (the order of message[:, i::sigma]).  The pad
+ * bits of the last byte are written as 0 and never counted.  sigma is in 1..8.
+ *   ideas_bits_to_tensor   z float [B][L]:  z = step * (num + 0.5) - 1 + ((jitter * r) * 2 - r),  step = 2 / 2^sigma,
+ *                          r = (float)(step * delta) (the product in double, rounded once), num = the element's sigma bits as an
+ *                          integer, every step one f32 operation in that order: bitwise utils.message_to_tensor.  jitter: U[0,1)
+ *                          float [B][L], or NULL: the jitter term is skipped (z is the bin centre).
+ *   ideas_tensor_to_bits   z [B][L], f32 or bf16 (widened exactly):  n = (min(max(z, -1), 1) + 1.0f) / step in f32 -- the f32
+ *                          rounding of the "+ 1" is part of the reference's decision -- q = min(floor(n), 2^sigma - 1), bit i of the
+ *                          element = (q >> (sigma - 1 - i)) & 1: bitwise utils.tensor_to_message.  A NaN decodes as zeros.
+ *                          bits (packed rows, may be NULL) receives the decisions; n_err (int [B], may be NULL; needs ref_bits,
+ *                          packed rows) receives the number of message bits of image b that differ from ref_bits.  One workgroup per
+ *                          image, a fixed-order reduction and one plain store: no atomics, nothing to clear, reproducible.
+ *   ideas_image_f32_to_u8  x [B,C,H,W] stored as `layout` (IDEAS_NCHW or IDEAS_NHWC), f32 or bf16, C = 1 or 3.  u8 [B][H][W][C]:
+ *                              u8 = trunc(clamp(((clamp(x, -1, 1) + 1) / 2) * 255 + 0.5, 0, 255))
+ *                          each step rounded to f32 (utils.image_grid / torchvision's save_image(normalize=True, range=(-1, 1)));
+ *                          a NaN gives 0.  y (optional, float [B][H][W][C]) = (u8 / 255 - 0.5) / 0.5, bitwise what
+ *                          ideas_image_u8_to_f32 makes of u8: the image a receiver decodes from the file.  NHWC moves four elements
+ *                          a lane (16-byte loads and stores of floats) when x, u8 and y are 16-byte aligned, one element otherwise.
+ * IDEAS_E_NULL: a required pointer is NULL (z; bits of the encoder; both outputs of the decoder; n_err without ref_bits; u8; x).
+ * IDEAS_E_SHAPE: B, L, H or W <= 0, C other than 1 or 3.  IDEAS_E_UNSUPPORTED: sigma outside 1..8, a dtype other than f32 / bf16,
+ * an unknown layout.  Every check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+int ideas_bits_to_tensor(float* z, const void* bits, const float* jitter, int B, int L, int sigma, float delta, void* stream);
+int ideas_tensor_to_bits(void* bits, int* n_err, const void* z, const void* ref_bits, int B, int L, int sigma, int dtype,
+                         void* stream);
+int ideas_image_f32_to_u8(void* u8, float* y, const void* x, int B, int C, int H, int W, int layout, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

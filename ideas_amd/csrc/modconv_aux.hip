@@ -189,8 +189,8 @@ __global__ __launch_bounds__(256) void act_bwd_dot_kernel(T* __restrict__ gpre, 
     auto rows = [&](int c4, int pr, int R) {
         struct { double x, y, z, w; } accd = {0.0, 0.0, 0.0, 0.0}, accb = {0.0, 0.0, 0.0, 0.0};
         const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        // optional per-(b, c) factor on the stored gradient only (bf16 path: the demodulation d[b,c], so that the input- and
-        // weight-gradient kernels need no per-sample input scale); bias_grad / dot are taken before it
+        // optional per-(b, c) factor on the stored gradient only (meant for the demodulation d[b,c], so that the input- and
+        // weight-gradient kernels need no per-sample input scale; op/modulated_conv.py passes NULL); bias_grad / dot are taken before it
         const float4 gs = gscale ? *reinterpret_cast<const float4*>(gscale + (int64_t)b * C + c4 * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
         for (int64_t pp = p0 + pr; pp < p1; pp += R) {
             const int64_t off = base + pp * C + c4 * 4;
@@ -313,7 +313,8 @@ extern "C" int ideas_act_bwd_dot(void* gpre, float* bias_grad, double* dot, cons
     if (!gpre || !bias_grad || !dot || !gy || !out) return IDEAS_E_NULL;
     if (B <= 0 || P <= 0 || C <= 0 || C > 3072 || B > 65535) return IDEAS_E_SHAPE;
     if (C & 3) return IDEAS_E_ALIGN;
-    if (!ideas_aligned16(gpre) || !ideas_aligned16(gy) || !ideas_aligned16(out) || (bias && !ideas_aligned16(bias)))
+    if (!ideas_aligned16(gpre) || !ideas_aligned16(gy) || !ideas_aligned16(out) || (bias && !ideas_aligned16(bias)) ||
+        (gpre_scale && !ideas_aligned16(gpre_scale)))       // both are read as float4 (C % 4 == 0 keeps every row of gpre_scale aligned)
         return IDEAS_E_ALIGN;
     int64_t chunks = ideas_cdiv(2048, B);
     const int64_t max_chunks = ideas_cdiv(P, 64);

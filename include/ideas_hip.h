@@ -371,7 +371,10 @@ int ideas_demod_wgrad(float* gw, const float* w, const float* gq, const float* s
 
 /* Per-(b,c) sum over pixels of a[b,p,c]*g[b,p,c] (NHWC).  Gives d(style) and d(demod) of the modulated conv
  * without materialising per-sample weights.  out must be ZEROED double[B*C]: products and sums are double throughout (the kernel is
- * HBM-bound; see ideas_demod_bwd for why the width matters).  C <= 6144. */
+ * HBM-bound; see ideas_demod_bwd for why the width matters).  C <= 6144, B <= 65535 (IDEAS_E_SHAPE above).
+ * IDEAS_E_ALIGN: C % 4 == 0 and a or g not 16-byte aligned (the rows are then read four channels at a time); IDEAS_BF16 with
+ * C % 4 != 0 (only f32 has the element-wise path; a caller with such bf16 tensors converts them to f32 first).
+ * IDEAS_E_UNSUPPORTED: a dtype other than IDEAS_F32 / IDEAS_BF16.  Every check comes before any launch. */
 int ideas_pixel_dot(double* out, const void* a, const void* g, int B, int64_t P, int C, int dtype, void* stream);
 
 /* Backward prologue of a fused (modulated conv + bias + leaky-ReLU), NHWC, C % 4 == 0.  One pass over the incoming
@@ -380,8 +383,12 @@ int ideas_pixel_dot(double* out, const void* a, const void* g, int B, int64_t P,
  *     bias_grad[c] += sum_{b,p} gpre                       (ZEROED float[C])
  *     dot[b,c]     += sum_p gpre * (inverse_act(out) - bias[c])   (ZEROED double[B*C]; = <gpre, demodulated conv output>; C <= 3072)
  * so neither the pre-activation tensor nor a separate bias-gradient / pixel-dot pass is needed.
- * gpre_scale (optional float[B*C]): the STORED gpre is multiplied by it (bias_grad and dot are not) -- the bf16 path passes
- * the demodulation factor here, so its input- and weight-gradient kernels take the already-scaled gradient. */
+ * gpre_scale (optional float[B*C], 16-byte aligned like bias: both are read four channels at a time): the STORED gpre is
+ * multiplied by it (bias_grad and dot are not).  It is meant for the demodulation factor, so that input- and weight-gradient
+ * kernels could take the already-scaled gradient; the Python side (op/modulated_conv.py) passes NULL in every precision today and
+ * hands the factor to those kernels as their per-sample input scale instead.
+ * IDEAS_E_ALIGN: C % 4 != 0, or gpre, gy, out, bias or gpre_scale not 16-byte aligned.  IDEAS_E_SHAPE: C > 3072, B > 65535, a
+ * non-positive size.  Every check comes before any launch. */
 int ideas_act_bwd_dot(void* gpre, float* bias_grad, double* dot, const void* gy, const void* out, const float* bias,
                       const float* gpre_scale, int B, int64_t P, int C, float alpha, float act_gain, int dtype, void* stream);
 

@@ -35,7 +35,7 @@
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
 #include "conv_epilogue.hpp"
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -376,12 +376,12 @@ int launch_b3_multi_cfg(int n, void* y, const void* x, const void* const* wplane
         a.w[i] = wplanes[i];
         a.off[i] = (int)blocks;
         blocks += ideas_cdiv((int64_t)ps[i].B * ps[i].OH * ps[i].OW, BM_) * a.tiles_n;
-        if (blocks > 0x7fffffffLL) return IDEAS_E_SHAPE;
+        if (!ideas_grid_fits(blocks)) return IDEAS_E_SHAPE;
     }
     for (int i = n; i < 4; ++i) { a.p[i] = ps[0]; a.w[i] = wplanes[0]; a.off[i] = (int)blocks; }
     a.off[n] = (int)blocks;
     a.off[4] = (int)blocks;
-    const unsigned x_bytes = (unsigned)((int64_t)ps[0].B * ps[0].IH * ps[0].IW * ps[0].Cin * 4);
+    const unsigned x_bytes = ideas_x_bytes(ps, 4);
     if (in_scale)
         hipLaunchKernelGGL((conv_b3_multi_kernel<WM, WN, MT, NT, true>), dim3((unsigned)blocks), dim3(256), 0, stream, (float*)y,
                            (const float*)x, in_scale, out_scale, a, x_bytes);
@@ -398,18 +398,14 @@ int launch_b3_cfg(void* y, const void* x, const void* wplanes, const float* in_s
     const int64_t M = (int64_t)p->B * p->OH * p->OW;
     const int64_t tm = ideas_cdiv(M, BM_);
     const int tn = (int)ideas_cdiv(p->Cout, BN_);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_x_bytes(p, 4);
     const unsigned plane_bytes = (unsigned)((int64_t)p->TY * p->TX * p->Cin * p->Cout * 2);
-    auto go = [&](auto sc, auto rf) {
+    with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) {
         hipLaunchKernelGGL((conv_b3_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value>),
                            dim3((unsigned)(tm * tn)), dim3(256), 0, stream, (float*)y, (const float*)x, wplanes,
                            in_scale, out_scale, bias, (const float*)resid, *p, tn, x_bytes, plane_bytes);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    });
     return ideas_launch_status();
 }
 
@@ -467,7 +463,7 @@ extern "C" int ideas_b3_split_weights(void* planes, const void* wmat, int Cout, 
     if (Cout <= 0 || K <= 0 || Cin <= 0 || K % Cin) return IDEAS_E_SHAPE;
     if (Cin % 16 || !ideas_aligned16(planes) || !ideas_aligned16(wmat)) return IDEAS_E_ALIGN;
     const int64_t n4 = (int64_t)Cout * (K / 4);
-    const int blocks = (int)(n4 / 256 + 1 < 2048 ? n4 / 256 + 1 : 2048);
+    const int blocks = ideas_prep_blocks(n4);
     hipLaunchKernelGGL(split_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes,
                        (const float4*)wmat, Cout, K, Cin);
     return ideas_launch_status();
@@ -479,7 +475,7 @@ extern "C" int ideas_b3_split_weights_strided(void* planes, const float* w, int 
     if (Cout <= 0 || TY <= 0 || TX <= 0 || Cin <= 0) return IDEAS_E_SHAPE;
     if (Cin % 16 || !ideas_aligned16(planes)) return IDEAS_E_ALIGN;
     const int64_t n4 = (int64_t)Cout * TY * TX * (Cin / 4);
-    const int blocks = (int)(n4 / 256 + 1 < 2048 ? n4 / 256 + 1 : 2048);
+    const int blocks = ideas_prep_blocks(n4);
     const bool unit = sc == 1 && ideas_aligned16(w) && sn % 4 == 0 && sty % 4 == 0 && stx % 4 == 0;
     if (unit)
         hipLaunchKernelGGL(split_weights_strided_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes, w, Cout,

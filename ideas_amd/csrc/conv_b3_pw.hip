@@ -23,7 +23,7 @@
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
 #include "conv_epilogue.hpp"
-#include <cstdlib>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -506,8 +506,7 @@ __global__ __launch_bounds__(256, 2) void conv_b3_pw_wgrad_kernel(float* __restr
 // per-sample scales and without accumulation, Cin % 16 == 0 up to 128 or Cin % 128 == 0 up to 1024, tensors below 4 GB.
 // IDEAS_B3_PW=0: never (A/B).
 int ideas_b3_pw_ok(const ideas_conv_params* p, const float* in_scale, const float* out_scale, const void* resid) {
-    const char* e = getenv("IDEAS_B3_PW");
-    if (e && e[0] == '0') return 0;
+    if (ideas_env_off("IDEAS_B3_PW")) return 0;
     if (in_scale || out_scale || p->accumulate || p->reflect) return 0;
     if (p->TY != 1 || p->TX != 1 || p->sy != 1 || p->sx != 1 || p->offy != 0 || p->offx != 0) return 0;
     if (p->osy != 1 || p->osx != 1 || p->ooy != 0 || p->oox != 0) return 0;
@@ -554,8 +553,7 @@ int ideas_b3_pw_fwd(void* y, const void* x, const void* wplanes, const float* bi
 
 // Weight gradient of the same flat geometry (no per-sample scales), Cin % 64 == 0 and Cout % 64 == 0.  IDEAS_B3_PW_WGRAD=0: never.
 int ideas_b3_pw_wgrad_ok(const ideas_conv_params* p, const float* in_scale, const float* out_scale) {
-    const char* e = getenv("IDEAS_B3_PW_WGRAD");
-    if (e && e[0] == '0') return 0;
+    if (ideas_env_off("IDEAS_B3_PW_WGRAD")) return 0;
     if (in_scale || out_scale || p->reflect) return 0;
     if (p->TY != 1 || p->TX != 1 || p->sy != 1 || p->sx != 1 || p->offy != 0 || p->offx != 0) return 0;
     if (p->osy != 1 || p->osx != 1 || p->ooy != 0 || p->oox != 0) return 0;
@@ -565,17 +563,22 @@ int ideas_b3_pw_wgrad_ok(const ideas_conv_params* p, const float* in_scale, cons
     return M >= 512 && (M + 64) * p->Cin * 4 < 0xffffffffLL && (M + 64) * p->Cout * 4 < 0xffffffffLL;
 }
 
+// split-K plan: pixels in steps of 32.  Unique here: a target in blocks (about four rounds of the 512 resident ones), not in waves,
+// and ranges of at least 256 pixels (rounding down).
+ideas_plan ideas_b3_pw_wgrad_plan(const ideas_conv_params* p, int, int64_t blocks) {
+    if (blocks <= 0) blocks = 2048;
+    const int64_t M = (int64_t)p->B * p->OH * p->OW, tiles = (int64_t)(p->Cout / 64) * (p->Cin / 64);
+    int64_t ranges = std::max<int64_t>(blocks / tiles, 1);
+    if (M / ranges < 256) ranges = std::max<int64_t>(M / 256, 1);
+    return {splitk_round(M, ranges, 32), blocks};
+}
+
 int ideas_b3_pw_wgrad(float* gw, const void* gy, const void* x, const ideas_conv_params* p, hipStream_t stream) {
     const int64_t M = (int64_t)p->B * p->OH * p->OW;
     const int tiles_ci = p->Cin / 64, tiles = (p->Cout / 64) * tiles_ci;
-    // about four rounds of the 512 resident blocks, >= 256 pixels per range (multiples of the 32-pixel step)
-    int64_t ranges = 2048 / tiles;
-    if (ranges < 1) ranges = 1;
-    if (M / ranges < 256) ranges = M / 256 > 0 ? M / 256 : 1;
-    int64_t per = ideas_cdiv(ideas_cdiv(M, ranges), 32) * 32;
-    ranges = ideas_cdiv(M, per);
-    if ((int64_t)tiles * ranges > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    hipLaunchKernelGGL(conv_b3_pw_wgrad_kernel, dim3(splitk_grid(tiles, ranges)), dim3(256), 0, stream, gw, (const float*)gy,
-                       (const float*)x, *p, (unsigned)M, tiles_ci, tiles, (int)ranges, (unsigned)per);
+    const SplitK k = ideas_b3_pw_wgrad_plan(p, 0, 0).k;
+    if (!ideas_grid_fits((int64_t)tiles * k.splits)) return IDEAS_E_SHAPE;
+    hipLaunchKernelGGL(conv_b3_pw_wgrad_kernel, dim3(splitk_grid(tiles, k.splits)), dim3(256), 0, stream, gw, (const float*)gy,
+                       (const float*)x, *p, (unsigned)M, tiles_ci, tiles, (int)k.splits, (unsigned)k.per);
     return ideas_launch_status();
 }

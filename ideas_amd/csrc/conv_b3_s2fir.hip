@@ -29,7 +29,7 @@
 #ifndef S2FIR_DPP_BUILTIN
 #define S2FIR_DPP_BUILTIN 0
 #endif
-#include <cstdlib>
+#include "conv_launch.hpp"
 
 #ifndef S2FIR_XB_AUX
 // Cache policy of the side-output stores (A/B builds: -DS2FIR_XB_AUX=n; 0 = default, 1 = sc0, 2 = nt, 3 = sc0 nt).  A store
@@ -388,9 +388,8 @@ int launch_s2fir(void* y, void* xb, const void* x, const void* wplanes, const fl
     constexpr int BN = WN * NB * 32;
     const int64_t tm = (int64_t)p->B * ideas_cdiv(p->OH, TR) * ideas_cdiv(p->OW, TP);
     const int tn = (int)ideas_cdiv(p->Cout, BN);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * f.XH * f.XW * p->Cin * 4);
-    const unsigned xb_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_nhwc_bytes(p->B, f.XH, f.XW, p->Cin, 4), xb_bytes = ideas_x_bytes(p, 4);
     const unsigned plane_bytes = (unsigned)((int64_t)9 * p->Cin * p->Cout * 2);
     if (xb)
         hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, true, 0, MOD>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)xb,
@@ -407,11 +406,11 @@ int launch_s2img(void* y, const void* x, const void* wplanes, const float* in_sc
     constexpr int BN = WN * NB * 32;
     const int64_t tm = (int64_t)p->B * ideas_cdiv(p->OH, TR) * ideas_cdiv(p->OW, TP);
     const int tn = (int)ideas_cdiv(p->Cout, BN);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
     S2Fir f;
     for (int i = 0; i < 4; ++i) f.kh[i] = f.kv[i] = 0.f;
     f.XH = p->IH; f.XW = p->IW; f.pad0 = 0;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
+    const unsigned x_bytes = ideas_x_bytes(p, 4);
     const unsigned plane_bytes = (unsigned)((int64_t)9 * p->Cin * p->Cout * 2);
     hipLaunchKernelGGL((conv_b3_s2fir_kernel<NCW, WN, NB, false, 1>), dim3((unsigned)(tm * tn)), dim3((NCW + NPW) * 64), 0, stream, (float*)y, (float*)nullptr,
                        (const float*)x, wplanes, bias, (const float*)resid, *p, f, tn, x_bytes, plane_bytes, 0u, in_scale, out_scale);

@@ -28,8 +28,7 @@
 //  unpack_f32_isa_counts.txt)
 #include "b3.hpp"
 #include "conv_epilogue.hpp"
-#include <cstdlib>
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -331,8 +330,7 @@ static bool tphase_match(int n, const ideas_conv_params* ps, int (&order)[4]) {
 
 // 16-byte stores of the epilogue where the output allows them; IDEAS_B3_TPHASE_STORE=0 (read per call) keeps the one-dword stores
 static bool tphase_store16(const void* y, int Cout) {
-    const char* es = getenv("IDEAS_B3_TPHASE_STORE");
-    return !(es && es[0] == '0') && Cout % 4 == 0 && ideas_aligned16(y);
+    return !ideas_env_off("IDEAS_B3_TPHASE_STORE") && Cout % 4 == 0 && ideas_aligned16(y);
 }
 // (for tests and A/B scripts: 1 when a launch of conv_b3_tphase_kernel writing Cout channels at y takes the 16-byte stores under the
 // present environment; a diagnostic that is not part of the ABI of include/ideas_hip.h and not bound by ideas_amd/_lib.py)
@@ -367,17 +365,12 @@ int ideas_b3_fwd_tphase(int n, void* y, const void* x, const void* const* wplane
     const int QH = exact ? p.IH : p.OH, QW = exact ? p.IW : p.OW;       // (the 2x2-tap phase covers every input-grid position)
     const int64_t tm = (int64_t)p.B * ((QH + PH - 1) / PH) * ((QW + PW - 1) / PW);
     const int tn = (p.Cout + 127) / 128;
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p.B * p.IH * p.IW * p.Cin * 4);
-    const bool st16 = tphase_store16(y, p.Cout);
-    auto go = [&](auto sc, auto s16) {
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_x_bytes(&p, 4);
+    with_flags(in_scale != nullptr, tphase_store16(y, p.Cout), [&](auto sc, auto s16) {
         hipLaunchKernelGGL((conv_b3_tphase_kernel<decltype(sc)::value, decltype(s16)::value>), dim3((unsigned)(tm * tn)), dim3(256), 0, stream,
                            (float*)y, (const float*)x, in_scale, out_scale, p, a, QH, QW, tn, x_bytes);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (st16) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (st16) go(F{}, T{}); else go(F{}, F{}); }
+    });
     if (exact) {
         // position row IH: phases (2x2) and (2x1) [output row 2 IH, even / odd columns]; position column IW, rows < IH: phases (2x2), (1x2)
         const int rowph[2] = {0, 1}, colph[2] = {0, 2};

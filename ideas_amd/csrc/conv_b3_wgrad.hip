@@ -22,7 +22,7 @@
 //  profiles/unpack_f32_family_ab.txt -- the plain operators stay, see b3.hpp)
 #define B3_UNPACK_F32 0
 #include "b3.hpp"
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -209,60 +209,38 @@ __global__ __launch_bounds__(256, 2) void conv_b3_wgrad_kernel(float* __restrict
     }
 }
 
-template <int WM, int WN, int MT, int NT>
+// the tiles <WM, WN, MT, NT> by output channels
+template <typename F> int b3_wgrad_tile(const ideas_conv_params* p, F f) {
+    if (p->Cout <= 64) return f(ideas_tile<2, 2, 1, 3>{});   // 64 (o) x 192 (k)
+    return f(ideas_tile<2, 2, 2, 2>{});                      // 128 (o) x 128 (k)
+}
+
+// (the <scaled, zero-padded> instantiation answers for all four variants)
+template <typename T> int64_t b3_wgrad_slots() {
+    return (int64_t)ideas_cu_count() * ideas_blocks_per_cu<conv_b3_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, true, false>>(256);
+}
+
+// split-K plan: pixels in steps of 16, >= 16 steps per block, whole waves.  Two waves of resident blocks -- four where every block
+// still reduces >= 4096 pixels: the long reductions of the 128-512 channel layers at >= 64x64 gain 4-6 % from the finer interleaving
+// (164 -> 170, 169 -> 179 TFLOP/s), short ones lose to the extra atomics (E.2.conv1: 152 -> 123), profiles/r02_wgrad_ab.txt
+SplitK b3_wgrad_plan(const ideas_conv_params* p, int BM_, int BN_, int64_t slots) {
+    const int64_t P = (int64_t)p->B * p->OH * p->OW;
+    const int64_t tiles = ideas_cdiv(p->Cout, BM_) * ideas_cdiv(p->TY * p->TX * p->Cin, BN_);
+    const int64_t splits = std::min({splitk_target(slots, tiles, P, 4096), ideas_cdiv(P, 16 * 16), (int64_t)65535});
+    return splitk_whole_waves(splitk_round(P, splits, 16), P, 16, tiles, slots);
+}
+
+template <typename T>
 int launch_b3_wgrad_cfg(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale,
                         const ideas_conv_params* p, hipStream_t stream) {
-    constexpr int BM_ = WM * MT * 32, BN_ = WN * NT * 32;
-    const int64_t P = (int64_t)p->B * p->OH * p->OW;
-    const int Ktot = p->TY * p->TX * p->Cin;
-    const int tm = (int)ideas_cdiv(p->Cout, BM_);
-    const int tn = (int)ideas_cdiv(Ktot, BN_);
-    const int64_t tiles = (int64_t)tm * tn;
-    static int occ = 0, n_cu = 0;
-    if (!occ) {
-        int o = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, conv_b3_wgrad_kernel<WM, WN, MT, NT, true, false>, 256, 0);
-        occ = (e == hipSuccess && o > 0) ? o : 2;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    // split-K sizing as in conv_igemm.hip: whole waves of resident blocks, >= 16 steps per block
-    const int64_t slots = (int64_t)occ * n_cu;
-    const int64_t max_splits = ideas_cdiv(P, 16 * 16);
-    // two waves of resident blocks -- four where every block still reduces >= 4096 pixels: the long reductions of the 128-512
-    // channel layers at >= 64x64 gain 4-6 % from the finer interleaving (164 -> 170, 169 -> 179 TFLOP/s), short ones lose to the
-    // extra atomics (E.2.conv1: 152 -> 123), profiles/r02_wgrad_ab.txt
-    int64_t splits = (4 * slots) / tiles;
-    if (splits < 1 || P / splits < 4096) splits = (2 * slots) / tiles;
-    if (splits < 1) splits = 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 65535) splits = 65535;
-    int64_t per = ideas_cdiv(ideas_cdiv(P, splits), 16) * 16;
-    splits = ideas_cdiv(P, per);
-    {
-        const int64_t blocks = tiles * splits;
-        const int64_t waves = blocks / slots;
-        if (waves >= 1 && blocks % slots) {
-            const int64_t want = (waves * slots) / tiles;
-            if (want >= 1) {
-                per = ideas_cdiv(ideas_cdiv(P, want), 16) * 16;
-                splits = ideas_cdiv(P, per);
-            }
-        }
-    }
-    const unsigned gy_bytes = (unsigned)((int64_t)p->B * p->YH * p->YW * p->Cout * 4);
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
-    auto go = [&](auto sc, auto rf) {
-        hipLaunchKernelGGL((conv_b3_wgrad_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value>),
-                           dim3(splitk_grid(tiles, splits)), dim3(256), 0, stream, gw, (const float*)gy,
-                           (const float*)x, in_scale, out_scale, *p, tn, (int)per, gy_bytes, x_bytes, (int)tiles, (int)splits);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool sc = in_scale && out_scale;
-    if (sc) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    const int tn = (int)ideas_cdiv(p->TY * p->TX * p->Cin, T::BN);
+    const int64_t tiles = ideas_cdiv(p->Cout, T::BM) * tn;
+    const SplitK k = b3_wgrad_plan(p, T::BM, T::BN, b3_wgrad_slots<T>());
+    with_flags(in_scale && out_scale, p->reflect, [&](auto sc, auto rf) {
+        hipLaunchKernelGGL((conv_b3_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, decltype(sc)::value, decltype(rf)::value>),
+                           dim3(splitk_grid(tiles, k.splits)), dim3(256), 0, stream, gw, (const float*)gy, (const float*)x, in_scale,
+                           out_scale, *p, tn, (int)k.per, ideas_gy_bytes(p, 4), ideas_x_bytes(p, 4), (int)tiles, (int)k.splits);
+    });
     return ideas_launch_status();
 }
 
@@ -284,6 +262,15 @@ extern "C" int ideas_b3_wgrad_supported(const ideas_conv_params* p) {
 // called by ideas_conv_wgrad for dtype IDEAS_F32_B3 once the arguments are validated and ideas_b3_wgrad_supported
 int ideas_b3_wgrad(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale,
                    const ideas_conv_params* p, hipStream_t stream) {
-    if (p->Cout <= 64) return launch_b3_wgrad_cfg<2, 2, 1, 3>(gw, gy, x, in_scale, out_scale, p, stream);   // 64 (o) x 192 (k)
-    return launch_b3_wgrad_cfg<2, 2, 2, 2>(gw, gy, x, in_scale, out_scale, p, stream);   // 128 (o) x 128 (k)
+    return b3_wgrad_tile(p, [&](auto t) { return launch_b3_wgrad_cfg<decltype(t)>(gw, gy, x, in_scale, out_scale, p, stream); });
+}
+
+ideas_plan ideas_b3_wgrad_plan(const ideas_conv_params* p, int, int64_t slots) {
+    SplitK k;
+    b3_wgrad_tile(p, [&](auto t) {
+        if (slots <= 0) slots = b3_wgrad_slots<decltype(t)>();
+        k = b3_wgrad_plan(p, t.BM, t.BN, slots);
+        return 0;
+    });
+    return {k, slots};
 }

@@ -31,8 +31,18 @@
 //
 // Requires TY = TX = 3, dilation 1, S in {1, 2}, OW % 16 == 0, Cin % 64 == 0, Cout % 64 == 0, dense G (osy = osx = 1).
 #include "b3.hpp"
-#include <type_traits>
-#include <cstdlib>
+#include "conv_launch.hpp"
+
+// split-K plan: the rows B * OH of each 16-column strip, one row a step, >= 16 rows per range.  About four waves of the 512 resident
+// slots (2 per CU) where a range still has >= 128 rows, two otherwise.  Unique here: the waves count tiles x strips, the cap rounds
+// DOWN (rows / 16), no whole-waves pass.
+ideas_plan ideas_b3_wgrad3_plan(const ideas_conv_params* p, int, int64_t slots) {
+    if (slots <= 0) slots = 512;
+    const int64_t tiles = (int64_t)(p->Cout / 64) * (p->Cin / 64), strips = p->OW / 16, rows_total = (int64_t)p->B * p->OH;
+    const int64_t spl = std::min(splitk_target(slots, tiles * strips, rows_total, 128), std::max<int64_t>(rows_total / 16, 1));
+    const SplitK k = splitk_round(rows_total, spl, 1);
+    return {{k.splits * strips, k.per}, slots};                // (splits = ranges of rows x strips)
+}
 
 namespace {
 
@@ -288,44 +298,25 @@ __global__ __launch_bounds__(256, 2) void conv_b3_wgrad3_kernel(float* __restric
 // (a stride-2 variant with TWO window rows per barrier was built in round 5, measured at parity with the kernel above -- 0.93-1.06x,
 // profiles/r05_wgrad3_s2_ab.txt -- and left the library in round 6: tools/attic/conv_b3_wgrad3_s2pair.hip)
 
+
 template <int S>
 int launch_wgrad3(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale, const ideas_conv_params* p,
                   hipStream_t stream) {
     const int tiles_ci = p->Cin / 64, tiles = (p->Cout / 64) * tiles_ci;
     const int strips = p->OW / 16;
-    const int64_t rows_total = (int64_t)p->B * p->OH;
-    // blocks: about four waves of the 512 resident slots (2 per CU) where a range still has >= 128 rows, two otherwise; >= 16 rows
-    const int64_t slots = 512;
-    int64_t spl = (4 * slots) / ((int64_t)tiles * strips);
-    if (spl < 1 || rows_total / spl < 128) spl = (2 * slots) / ((int64_t)tiles * strips);
-    if (spl < 1) spl = 1;
-    const int64_t max_spl = rows_total / 16 > 0 ? rows_total / 16 : 1;
-    if (spl > max_spl) spl = max_spl;
-    int64_t per = ideas_cdiv(rows_total, spl);
-    spl = ideas_cdiv(rows_total, per);
-    const int64_t splits = spl * strips;
-    if ((int64_t)tiles * splits > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned gy_bytes = (unsigned)((int64_t)p->B * p->YH * p->YW * p->Cout * 4);
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
-    auto go = [&](auto sc, auto rf) {
-        hipLaunchKernelGGL((conv_b3_wgrad3_kernel<S, decltype(sc)::value, decltype(rf)::value>), dim3(splitk_grid(tiles, splits)),
+    const SplitK k = ideas_b3_wgrad3_plan(p, 0, 0).k;
+    if (!ideas_grid_fits(tiles * k.splits)) return IDEAS_E_SHAPE;
+    with_flags(in_scale && out_scale, p->reflect, [&](auto sc, auto rf) {
+        hipLaunchKernelGGL((conv_b3_wgrad3_kernel<S, decltype(sc)::value, decltype(rf)::value>), dim3(splitk_grid(tiles, k.splits)),
                            dim3(256), 0, stream, gw, (const float*)gy, (const float*)x, in_scale, out_scale, *p, tiles_ci, tiles,
-                           (int)splits, strips, (int)per, gy_bytes, x_bytes);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool sc = in_scale && out_scale;
-    if (sc) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+                           (int)k.splits, strips, (int)k.per, ideas_gy_bytes(p, 4), ideas_x_bytes(p, 4));
+    });
     return ideas_launch_status();
 }
 
 }  // namespace
 
-bool ideas_b3_wgrad3_enabled() {
-    const char* e = getenv("IDEAS_B3_WGRAD3");          // (read per call: no state in the library, include/ideas_hip.h)
-    return !(e && e[0] == '0');
-}
+bool ideas_b3_wgrad3_enabled() { return !ideas_env_off("IDEAS_B3_WGRAD3"); }
 
 extern "C" int ideas_b3_wgrad3_supported(const ideas_conv_params* p) {
     if (!p) return 0;
@@ -336,10 +327,7 @@ extern "C" int ideas_b3_wgrad3_supported(const ideas_conv_params* p) {
     // MFMAs in every other one.  Round 3 measured it 4-7 % SLOWER than conv_b3_wgrad.hip and kept it opt-in; with the address-free
     // transpose reads of round 4 it is ahead: same box, two interleaved runs of 32 iterations, 412.34 / 412.42 -> 411.49 / 411.78 ms
     // (tools/ab_step.sh).  IDEAS_B3_WGRAD3_S2=0 switches the stride-2 path off (A/B measurements).
-    if (p->sy == 2) {
-        const char* e = getenv("IDEAS_B3_WGRAD3_S2");
-        if (e && e[0] == '0') return 0;
-    }
+    if (p->sy == 2 && ideas_env_off("IDEAS_B3_WGRAD3_S2")) return 0;
     if (p->reflect && (p->IH < 2 || p->IW < 2)) return 0;
     // every window pixel the taps can address must lie inside what one strip stages: ix = ox*S + tx + offx, tx in 0..2
     if (p->offx > 0 || p->offx < -2 || p->offy > 0 || p->offy < -2) return 0;

@@ -28,8 +28,7 @@
 #ifndef WINO_ABL
 #define WINO_ABL 0
 #endif
-#include <cstdlib>
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -857,7 +856,7 @@ extern "C" int ideas_b3_wino_split_weights(void* planes, const void* w, int N, i
     if (N <= 0 || C <= 0) return IDEAS_E_SHAPE;
     if (C % 16 || !ideas_aligned16(planes)) return IDEAS_E_ALIGN;
     const int64_t total = (int64_t)N * 3 * (C / 4);
-    const int blocks = (int)(total / 256 + 1 < 2048 ? total / 256 + 1 : 2048);
+    const int blocks = ideas_prep_blocks(total);
     hipLaunchKernelGGL(wino_split_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes,
                        (const float*)w, N, C, sn, sky, skx, sc, base);
     return ideas_launch_status();
@@ -878,10 +877,9 @@ static WinoChoice wino_choose(int B, int IH, int IW, int Cin, int Cout) {
     c.wide = Cin % 32 == 0 && Cout > 64;
     c.tp = 0;
     c.nt256 = 0;
-    const char* e2d = getenv("IDEAS_B3_WINO2D");           // read per call: tests toggle it in-process
     const int W2 = IW / 2;
     const int TPsel = (W2 % 32 == 0) ? 32 : (W2 % 16 == 0) ? 16 : (W2 % 8 == 0) ? 8 : 0;
-    if (!c.wide || (e2d && e2d[0] == '0') || !TPsel || IH % (WP / TPsel) != 0) return c;
+    if (!c.wide || ideas_env_off("IDEAS_B3_WINO2D") || !TPsel || IH % (WP / TPsel) != 0) return c;
     c.tp = TPsel;
     if (Cout % (4 * WN) != 0) return c;
     const int64_t nt = ideas_cdiv((int64_t)B * IH * W2, WP) * (Cout / (4 * WN));
@@ -908,17 +906,16 @@ int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* 
     const WinoChoice ch = wino_choose(p->B, p->IH, p->IW, p->Cin, p->Cout);
     const bool wide = ch.wide;                              // 8-wave 64 x 128 tile, K-step 32
     const int tn = (int)ideas_cdiv(p->Cout, wide ? 2 * WN : WN);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 4);
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_x_bytes(p, 4);
     const unsigned plane_bytes = (unsigned)((int64_t)3 * p->Cin * p->Cout * 2);     // one (v, plane): 3*Cin/16 steps x Cout x 32 B
     // row-sharing patch kernel: 8-wave tile shapes whose image divides into TR x TP patches (IDEAS_B3_WINO2D=0: the kernel above)
     const int TPsel = ch.tp;
     // epilogue configuration (wino_finish_fast): IDEAS_B3_WINO_EPI=0 keeps the flag-testing tail everywhere (A/B measurements)
     int epi = EPI_GENERIC;
     {
-        const char* eepi = getenv("IDEAS_B3_WINO_EPI");
         const bool vec = p->Cout % 4 == 0 && ((((uintptr_t)y | (uintptr_t)resid | (uintptr_t)out_scale | (uintptr_t)bias) & 15) == 0);
-        if (!(eepi && eepi[0] == '0') && vec && !p->accumulate && (int64_t)p->B * p->IH * p->IW * p->Cout * 4 < 0xffffffffLL) {
+        if (!ideas_env_off("IDEAS_B3_WINO_EPI") && vec && !p->accumulate && (int64_t)p->B * p->IH * p->IW * p->Cout * 4 < 0xffffffffLL) {
             const bool ba = bias && p->act && p->alpha >= 0.f && p->alpha <= 1.f;
             if (!bias && !p->act && !resid) epi = out_scale ? EPI_OS : EPI_PLAIN;
             else if (ba && !resid) epi = out_scale ? EPI_OS_BA : EPI_BA;
@@ -936,11 +933,8 @@ int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* 
                                bias, (const float*)resid, *p, (int)ideas_cdiv(p->Cout, decltype(nb)::value * WN),
                                x_bytes, plane_bytes, (int)nt, epi);
         };
-        using T = std::true_type;
-        using F = std::false_type;
         auto go1 = [&](auto tp, auto nb) {
-            if (in_scale) { if (p->reflect) go2(T{}, T{}, tp, nb); else go2(T{}, F{}, tp, nb); }
-            else { if (p->reflect) go2(F{}, T{}, tp, nb); else go2(F{}, F{}, tp, nb); }
+            with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) { go2(sc, rf, tp, nb); });
         };
         auto go0 = [&](auto tp) {
             if (n256) go1(tp, std::integral_constant<int, 4>{}); else go1(tp, std::integral_constant<int, 2>{});
@@ -950,7 +944,7 @@ int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* 
         else go0(std::integral_constant<int, 8>{});
         return ideas_launch_status();
     }
-    auto go = [&](auto sc, auto rf) {
+    with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) {
         if (wide)
             hipLaunchKernelGGL((conv_b3_wino_kernel<decltype(sc)::value, decltype(rf)::value, 2>), dim3((unsigned)(tm * tn)),
                                dim3(512), 0, stream, (float*)y, (const float*)x, uplanes, in_scale, out_scale, bias,
@@ -959,10 +953,6 @@ int ideas_b3_wino_fwd(void* y, const void* x, const void* uplanes, const float* 
             hipLaunchKernelGGL((conv_b3_wino_kernel<decltype(sc)::value, decltype(rf)::value, 1>), dim3((unsigned)(tm * tn)),
                                dim3(256), 0, stream, (float*)y, (const float*)x, uplanes, in_scale, out_scale, bias,
                                (const float*)resid, *p, tn, x_bytes, plane_bytes, epi);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    });
     return ideas_launch_status();
 }

@@ -29,8 +29,7 @@
 //     * split-K (XCD-banded, common.hpp: splitk_xcd_map) with f32 atomics into the (flat-bucket) f32 gradient; for modulated convs every split lies
 //       inside one image and the per-sample scales d[b,o] * s[b,ci] are applied to the accumulator in the epilogue.
 #include "conv_epilogue.hpp"
-#include <type_traits>
-#include <cstdlib>
+#include "conv_launch.hpp"
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -362,12 +361,12 @@ int launch_bf16_multi_cfg(int n, void* y, const void* x, const void* const* wpac
         if (i < n) {
             const int64_t tm = per_image ? (int64_t)ps[k].B * a.tpi[i] : ideas_cdiv((int64_t)ps[k].B * ps[k].OH * ps[k].OW, BM_);
             blocks += tm * a.tiles_n;
-            if (blocks > 0x7fffffffLL) return IDEAS_E_SHAPE;
+            if (!ideas_grid_fits(blocks)) return IDEAS_E_SHAPE;
         }
     }
     a.off[n] = (int)blocks;
     a.off[4] = (int)blocks;
-    const unsigned x_bytes = (unsigned)((int64_t)ps[0].B * ps[0].IH * ps[0].IW * ps[0].Cin * 2);
+    const unsigned x_bytes = ideas_x_bytes(ps, 2);
     if (per_image)
         hipLaunchKernelGGL((conv_bf16_multi_kernel<WM, WN, MT, NT, true>), dim3((unsigned)blocks), dim3(64 * WM * WN), 0, stream, (bf16_t*)y,
                            (const bf16_t*)x, out_scale, a, x_bytes);
@@ -556,8 +555,7 @@ __global__ __launch_bounds__(512, 4) void conv_bf16_img_kernel(bf16_t* __restric
 }
 
 static int bf16_img_tp(const ideas_conv_params* p) {      // patch width of the image kernel for this geometry, 0 = not its geometry
-    const char* e = getenv("IDEAS_BF16_IMG");             // (read per call: the tests toggle it in-process)
-    if (e && e[0] == '0') return 0;
+    if (ideas_env_off("IDEAS_BF16_IMG")) return 0;
     if (p->TY != 3 || p->TX != 3 || p->sy != 1 || p->sx != 1 || p->osy != 1 || p->osx != 1 || p->ooy || p->oox) return 0;
     if (!((p->dy == 1 && p->offy == -1) || (p->dy == -1 && p->offy == 1)) || p->dx != p->dy || p->offx != p->offy) return 0;
     if (p->OH != p->IH || p->OW != p->IW || p->YH != p->OH || p->YW != p->OW) return 0;
@@ -572,8 +570,8 @@ int launch_bf16_img(void* y, const void* x, const void* wpack, int per_image, co
                     const ideas_conv_params* p, hipStream_t stream) {
     const int64_t tm = (int64_t)p->B * (p->OH / (256 / TP)) * (p->OW / TP);
     const int tn = (p->Cout + 64 * NT - 1) / (64 * NT);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 2);
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_x_bytes(p, 2);
     const unsigned w_bytes = (unsigned)((int64_t)(per_image ? p->B : 1) * 9 * p->Cin * p->Cout * 2);
     if (per_image)
         hipLaunchKernelGGL((conv_bf16_img_kernel<TP, NT, true>), dim3((unsigned)(tm * tn)), dim3(512), 0, stream, (bf16_t*)y, (const bf16_t*)x,
@@ -600,18 +598,14 @@ int launch_bf16_cfg(void* y, const void* x, const void* wpack, int per_image, co
     const int tpi = (int)ideas_cdiv((int64_t)p->OH * p->OW, BM_);
     const int64_t tm = per_image ? (int64_t)p->B * tpi : ideas_cdiv(M, BM_);
     const int tn = (int)ideas_cdiv(p->Cout, BN_);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 2);
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    const unsigned x_bytes = ideas_x_bytes(p, 2);
     const unsigned w_bytes = (unsigned)((int64_t)(per_image ? p->B : 1) * p->TY * p->TX * p->Cin * p->Cout * 2);
-    auto go = [&](auto pi, auto rf) {
+    with_flags(per_image, p->reflect, [&](auto pi, auto rf) {
         hipLaunchKernelGGL((conv_bf16_kernel<WM, WN, MT, NT, NST, decltype(pi)::value, decltype(rf)::value>), dim3((unsigned)(tm * tn)),
                            dim3(64 * WM * WN), 0, stream, (bf16_t*)y, (const bf16_t*)x, wpack, out_scale, bias, (const bf16_t*)resid, *p, tn,
                            tpi, x_bytes, w_bytes);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (per_image) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    });
     return ideas_launch_status();
 }
 
@@ -859,51 +853,37 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_wgrad_kernel(float* __
     }
 }
 
-template <int WM, int WN, int MT, int NT>
+// split-K plan: pixels in steps of 32, no whole-waves pass; `slots` = 2 resident blocks per CU (1 for an 8-wave tile), a constant.
+// Four waves of blocks where every block still reduces >= 4096 pixels, two otherwise: conv_b3_wgrad.hip; bf16: 572 -> 645 TFLOP/s on
+// 128->128 @256x256, 730 -> 789 on 256->512 @64x64.  Plain convs: >= 8 steps per block.  Unique to the modulated convs: whole splits
+// inside ONE image (spi of them, >= 4 steps each, the target divided by B rounding down).
+SplitK bf16_wgrad_plan(const ideas_conv_params* p, bool sc, int BM_, int BN_, int64_t slots) {
+    const int64_t P = (int64_t)p->B * p->OH * p->OW, img = (int64_t)p->OH * p->OW;
+    const int64_t tiles = ideas_cdiv(p->Cout, BM_) * ideas_cdiv(p->TY * p->TX * p->Cin, BN_);
+    const int64_t splits = splitk_target(slots, tiles, P, 4096);
+    if (sc) {
+        const int64_t spi = std::max<int64_t>(std::min(splits / p->B, ideas_cdiv(img, 32 * 4)), 1);
+        const SplitK k = splitk_round(img, spi, 32);
+        return {k.splits * p->B, k.per, k.splits};
+    }
+    const SplitK k = splitk_round(P, std::min(splits, ideas_cdiv(P, 32 * 8)), 32);
+    return {k.splits, k.per, 1};
+}
+template <typename T> constexpr int64_t bf16_wgrad_slots() { return (T::WM * T::WN == 8 ? 1 : 2) * 256; }
+
+template <typename T>
 int launch_bf16_wgrad_cfg(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale,
                           const ideas_conv_params* p, hipStream_t stream) {
-    constexpr int BM_ = WM * MT * 32, BN_ = WN * NT * 32;
-    const int64_t P = (int64_t)p->B * p->OH * p->OW;
-    const int Ktot = p->TY * p->TX * p->Cin;
-    const int tm = (int)ideas_cdiv(p->Cout, BM_);
-    const int tn = (int)ideas_cdiv(Ktot, BN_);
-    const int64_t tiles = (int64_t)tm * tn;
+    const int tn = (int)ideas_cdiv(p->TY * p->TX * p->Cin, T::BN);
+    const int64_t tiles = ideas_cdiv(p->Cout, T::BM) * tn;
     const bool sc = in_scale && out_scale;
-    const int64_t img = (int64_t)p->OH * p->OW;
-    // split-K: about two waves of resident blocks (2 per CU), >= 8 steps each; modulated convs: whole splits inside one image
-    const int64_t slots = (WM * WN == 8 ? 1 : 2) * 256;
-    // (four waves of blocks where every block still reduces >= 4096 pixels, two otherwise: conv_b3_wgrad.hip; bf16: 572 -> 645
-    //  TFLOP/s on 128->128 @256x256, 730 -> 789 on 256->512 @64x64)
-    int64_t splits = (4 * slots) / tiles;
-    if (splits < 1 || P / splits < 4096) splits = (2 * slots) / tiles;
-    if (splits < 1) splits = 1;
-    int64_t per, spi = 1;
-    if (sc) {
-        spi = splits / p->B;                         // splits per image
-        const int64_t max_spi = ideas_cdiv(img, 32 * 4);
-        if (spi > max_spi) spi = max_spi;
-        if (spi < 1) spi = 1;
-        per = ideas_cdiv(ideas_cdiv(img, spi), 32) * 32;
-        spi = ideas_cdiv(img, per);
-        splits = spi * p->B;
-    } else {
-        const int64_t max_splits = ideas_cdiv(P, 32 * 8);
-        if (splits > max_splits) splits = max_splits;
-        per = ideas_cdiv(ideas_cdiv(P, splits), 32) * 32;
-        splits = ideas_cdiv(P, per);
-    }
-    if (tiles * splits > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned gy_bytes = (unsigned)((int64_t)p->B * p->YH * p->YW * p->Cout * 2);
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 2);
-    auto go = [&](auto s_, auto rf) {
-        hipLaunchKernelGGL((conv_bf16_wgrad_kernel<WM, WN, MT, NT, decltype(s_)::value, decltype(rf)::value>),
-                           dim3(splitk_grid(tiles, splits)), dim3(64 * WM * WN), 0, stream, gw, (const bf16_t*)gy, (const bf16_t*)x,
-                           in_scale, out_scale, *p, tn, (int)per, (int)spi, gy_bytes, x_bytes, (int)tiles, (int)splits);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (sc) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    const SplitK k = bf16_wgrad_plan(p, sc, T::BM, T::BN, bf16_wgrad_slots<T>());
+    if (!ideas_grid_fits(tiles * k.splits)) return IDEAS_E_SHAPE;
+    with_flags(sc, p->reflect, [&](auto s_, auto rf) {
+        hipLaunchKernelGGL((conv_bf16_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, decltype(s_)::value, decltype(rf)::value>),
+                           dim3(splitk_grid(tiles, k.splits)), dim3(64 * T::WM * T::WN), 0, stream, gw, (const bf16_t*)gy, (const bf16_t*)x,
+                           in_scale, out_scale, *p, tn, (int)k.per, (int)k.spi, ideas_gy_bytes(p, 2), ideas_x_bytes(p, 2), (int)tiles, (int)k.splits);
+    });
     return ideas_launch_status();
 }
 
@@ -937,7 +917,7 @@ extern "C" int ideas_bf16_pack_weights(void* pack, const void* wmat, const float
     if (Cin % 32 || !ideas_aligned16(pack) || !ideas_aligned16(wmat) || (in_scale && !ideas_aligned16(in_scale))) return IDEAS_E_ALIGN;
     if (!in_scale && B != 1) return IDEAS_E_SHAPE;
     const int64_t n8 = (int64_t)Cout * (K / 8);
-    const int blocks = (int)(n8 / 256 + 1 < 2048 ? n8 / 256 + 1 : 2048);
+    const int blocks = ideas_prep_blocks(n8);
     hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks, in_scale ? B : 1), dim3(256), 0, (hipStream_t)stream_, (uint4*)pack,
                        (const float4*)wmat, in_scale, Cout, K, Cin);
     return ideas_launch_status();
@@ -954,7 +934,7 @@ extern "C" int ideas_bf16_pack_weights_strided(void* pack, const float* w, const
     if (Cin % 32 || !ideas_aligned16(pack) || (in_scale && !ideas_aligned16(in_scale))) return IDEAS_E_ALIGN;
     if (!in_scale && B != 1) return IDEAS_E_SHAPE;
     const int64_t n8 = (int64_t)Cout * TY * TX * (Cin / 8);
-    const int blocks = (int)(n8 / 256 + 1 < 2048 ? n8 / 256 + 1 : 2048);
+    const int blocks = ideas_prep_blocks(n8);
     const bool unit = sc == 1 && ideas_aligned16(w) && sn % 4 == 0 && sty % 4 == 0 && stx % 4 == 0;
     const dim3 grid(blocks, in_scale ? B : 1);
     if (unit)
@@ -966,6 +946,16 @@ extern "C" int ideas_bf16_pack_weights_strided(void* pack, const float* w, const
     return ideas_launch_status();
 }
 
+// the forward tiles <WM, WN, MT, NT> of ideas_bf16_fwd and ideas_bf16_fwd_multi
+// (`auto`: instantiated at its first call, which keeps the kernels' order in the code object)
+template <typename F> static auto bf16_fwd_tile(const ideas_conv_params* p, int per_image, F f) {
+    const int64_t rows = (int64_t)(per_image ? 1 : p->B) * p->OH * p->OW;
+    if (p->Cout >= 256 && rows >= 256) return f(ideas_tile<4, 2, 2, 2>{});   // 256 x 128, 8 waves
+    if (p->Cout > 64) return f(ideas_tile<2, 2, 2, 2>{});                    // 128 x 128
+    if (p->Cout > 32) return f(ideas_tile<2, 2, 2, 1>{});                    // 128 x 64
+    return f(ideas_tile<4, 1, 1, 1>{});                                      // 128 x 32
+}
+
 // called by ideas_conv_igemm / ideas_conv_wgrad for dtype IDEAS_BF16 once the arguments are validated
 int ideas_bf16_fwd(void* y, const void* x, const void* wpack, int per_image, const float* out_scale, const float* bias,
                    const void* resid, const ideas_conv_params* p, hipStream_t stream) {
@@ -974,26 +964,21 @@ int ideas_bf16_fwd(void* y, const void* x, const void* wpack, int per_image, con
     // 1-3 % on 512-channel layers only and loses badly below; a fourth LDS stage and a register-prefetch pipeline (fragments of
     // tile t+1 read under the MFMAs of tile t) both measured 3-5 % SLOWER than three stages + counted vmcnt.
     if (ideas_bf16_pw_ok(p, per_image, out_scale, y, resid)) return ideas_bf16_pw_fwd(y, x, wpack, bias, resid, p, stream);   // flat 1x1 (conv_bf16_pw.hip)
-    const int64_t rows = (int64_t)(per_image ? 1 : p->B) * p->OH * p->OW;
     if (const int tp = bf16_img_tp(p)) {                  // 3x3 / stride 1: the activation operand as an LDS image (IDEAS_BF16_IMG=0: off)
         if (p->Cout > 64) return launch_bf16_img_tp<2>(tp, y, x, wpack, per_image, out_scale, bias, resid, p, stream);
         return launch_bf16_img_tp<1>(tp, y, x, wpack, per_image, out_scale, bias, resid, p, stream);
     }
-    if (p->Cout >= 256 && rows >= 256) return launch_bf16_cfg<4, 2, 2, 2>(y, x, wpack, per_image, out_scale, bias, resid, p, stream);   // 256 x 128, 8 waves
-    if (p->Cout > 64) return launch_bf16_cfg<2, 2, 2, 2>(y, x, wpack, per_image, out_scale, bias, resid, p, stream);   // 128 x 128
-    if (p->Cout > 32) return launch_bf16_cfg<2, 2, 2, 1>(y, x, wpack, per_image, out_scale, bias, resid, p, stream);   // 128 x 64
-    return launch_bf16_cfg<4, 1, 1, 1>(y, x, wpack, per_image, out_scale, bias, resid, p, stream);                     // 128 x 32
+    return bf16_fwd_tile(p, per_image, [&](auto t) {
+        return launch_bf16_cfg<t.WM, t.WN, t.MT, t.NT>(y, x, wpack, per_image, out_scale, bias, resid, p, stream);
+    });
 }
 
 // ideas_conv_igemm_multi for dtype IDEAS_BF16 (conv_igemm.hip validates): n <= 4 launches sharing x / y / scales
 int ideas_bf16_fwd_multi(int n, void* y, const void* x, const void* const* wpack, int per_image, const float* out_scale,
                          const ideas_conv_params* ps, hipStream_t stream) {
-    const ideas_conv_params* p = ps;
-    const int64_t rows = (int64_t)(per_image ? 1 : p->B) * p->OH * p->OW;
-    if (p->Cout >= 256 && rows >= 256) return launch_bf16_multi_cfg<4, 2, 2, 2>(n, y, x, wpack, per_image, out_scale, ps, stream);
-    if (p->Cout > 64) return launch_bf16_multi_cfg<2, 2, 2, 2>(n, y, x, wpack, per_image, out_scale, ps, stream);
-    if (p->Cout > 32) return launch_bf16_multi_cfg<2, 2, 2, 1>(n, y, x, wpack, per_image, out_scale, ps, stream);
-    return launch_bf16_multi_cfg<4, 1, 1, 1>(n, y, x, wpack, per_image, out_scale, ps, stream);
+    return bf16_fwd_tile(ps, per_image, [&](auto t) {
+        return launch_bf16_multi_cfg<t.WM, t.WN, t.MT, t.NT>(n, y, x, wpack, per_image, out_scale, ps, stream);
+    });
 }
 
 // Tile-shape A/B for tools/bench_igemm.py --cfg (not part of the declared ABI; the production dispatch is ideas_bf16_fwd)
@@ -1215,8 +1200,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_wgrad3_kernel(float* __restr
 }
 
 static bool bf16_wgrad3_ok(const ideas_conv_params* p) {
-    const char* e = getenv("IDEAS_BF16_WGRAD3");          // (read per call: the tests toggle it in-process)
-    if (e && e[0] == '0') return false;
+    if (ideas_env_off("IDEAS_BF16_WGRAD3")) return false;
     if (p->TY != 3 || p->TX != 3 || p->sy != 1 || p->sx != 1 || p->dy != 1 || p->dx != 1) return false;
     if (p->osy != 1 || p->osx != 1 || p->ooy || p->oox || p->YH != p->OH || p->YW != p->OW) return false;
     if (p->OW % 32 || p->Cin % 64 || p->Cout % 64 || p->OH < 8) return false;
@@ -1226,32 +1210,29 @@ static bool bf16_wgrad3_ok(const ideas_conv_params* p) {
     return (int64_t)p->B * p->OH * p->OW * p->Cin * p->Cout >= 6000000000LL;
 }
 
+// split-K plan of the tap-fused kernel: a rule of its own -- PARTS of the rows of one image (a block's range lies inside one image):
+// about four waves of the 512 resident blocks (two per CU) while a part keeps >= 32 rows, at least 8 rows
+ideas_plan ideas_bf16_wgrad3_plan(const ideas_conv_params* p, int, int64_t slots) {   // {splits, rows per part, parts}
+    if (slots <= 0) slots = 512;
+    const int64_t strips = p->OW / 32, base = (int64_t)(p->Cout / 64) * (p->Cin / 64) * strips * p->B;
+    int64_t parts = std::max<int64_t>((4 * slots) / base, 1);
+    while (parts > 1 && p->OH / parts < 32) --parts;
+    if (parts > p->OH / 8) parts = std::max(p->OH / 8, 1);
+    const SplitK k = splitk_round(p->OH, parts, 1);
+    return {{strips * p->B * k.splits, k.per, k.splits}, slots};
+}
+
 int launch_bf16_wgrad3(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale, const ideas_conv_params* p,
                        hipStream_t stream) {
     const int tiles_ci = p->Cin / 64, tiles = (p->Cout / 64) * tiles_ci;
     const int strips = p->OW / 32;
-    // parts per image: about four waves of the 512 resident blocks (two per CU) while a part keeps >= 32 rows, at least 8 rows
-    const int64_t base = (int64_t)tiles * strips * p->B;
-    int64_t parts = (4 * 512) / base;
-    if (parts < 1) parts = 1;
-    while (parts > 1 && p->OH / parts < 32) --parts;
-    if (parts > p->OH / 8) parts = p->OH / 8 > 0 ? p->OH / 8 : 1;
-    const int rows = (int)ideas_cdiv(p->OH, parts);
-    parts = ideas_cdiv(p->OH, rows);
-    const int64_t splits = (int64_t)strips * p->B * parts;
-    if ((int64_t)tiles * splits > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const unsigned gy_bytes = (unsigned)((int64_t)p->B * p->YH * p->YW * p->Cout * 2);
-    const unsigned x_bytes = (unsigned)((int64_t)p->B * p->IH * p->IW * p->Cin * 2);
-    auto go = [&](auto s_, auto rf) {
-        hipLaunchKernelGGL((conv_bf16_wgrad3_kernel<decltype(s_)::value, decltype(rf)::value>), dim3(splitk_grid(tiles, splits)), dim3(256), 0,
-                           stream, gw, (const bf16_t*)gy, (const bf16_t*)x, in_scale, out_scale, *p, tiles_ci, tiles, (int)splits, strips,
-                           (int)parts, rows, gy_bytes, x_bytes);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool sc = in_scale && out_scale;
-    if (sc) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    const SplitK k = ideas_bf16_wgrad3_plan(p, 0, 0).k;
+    if (!ideas_grid_fits((int64_t)tiles * k.splits)) return IDEAS_E_SHAPE;
+    with_flags(in_scale && out_scale, p->reflect, [&](auto s_, auto rf) {
+        hipLaunchKernelGGL((conv_bf16_wgrad3_kernel<decltype(s_)::value, decltype(rf)::value>), dim3(splitk_grid(tiles, k.splits)), dim3(256),
+                           0, stream, gw, (const bf16_t*)gy, (const bf16_t*)x, in_scale, out_scale, *p, tiles_ci, tiles, (int)k.splits, strips,
+                           (int)k.spi, (int)k.per, ideas_gy_bytes(p, 2), ideas_x_bytes(p, 2));
+    });
     return ideas_launch_status();
 }
 
@@ -1259,7 +1240,15 @@ int ideas_bf16_wgrad(float* gw, const void* gy, const void* x, const float* in_s
                      const ideas_conv_params* p, hipStream_t stream) {
     if (bf16_wgrad3_ok(p)) return launch_bf16_wgrad3(gw, gy, x, in_scale, out_scale, p, stream);    // 3x3 / s1: tap-fused, rolling window
     // (an 8-wave 256 x 128 tile, the winner of the forward family, measured 22 % SLOWER here: half the blocks for the split-K)
-    if (p->Cout > 64) return launch_bf16_wgrad_cfg<2, 2, 2, 2>(gw, gy, x, in_scale, out_scale, p, stream);   // 128 (o) x 128 (k)
-    if (p->Cout > 32) return launch_bf16_wgrad_cfg<2, 2, 1, 2>(gw, gy, x, in_scale, out_scale, p, stream);   // 64 x 128
-    return launch_bf16_wgrad_cfg<1, 4, 1, 1>(gw, gy, x, in_scale, out_scale, p, stream);                     // 32 x 128
+    return ideas_wgrad_tile(p, [&](auto t) { return launch_bf16_wgrad_cfg<decltype(t)>(gw, gy, x, in_scale, out_scale, p, stream); });
+}
+
+ideas_plan ideas_bf16_wgrad_plan(const ideas_conv_params* p, int scaled, int64_t slots) {
+    SplitK k;
+    ideas_wgrad_tile(p, [&](auto t) {
+        if (slots <= 0) slots = bf16_wgrad_slots<decltype(t)>();
+        k = bf16_wgrad_plan(p, scaled != 0, t.BM, t.BN, slots);
+        return 0;
+    });
+    return {k, slots};
 }

@@ -17,7 +17,7 @@
 // MFMA roles, K order (ascending 16-channel slices) and the epilogue expression are conv_bf16_body's: the results are BITWISE the
 // generic kernel's (tests/test_ops_gpu.py).
 #include "conv_epilogue.hpp"
-#include <cstdlib>
+#include "conv_launch.hpp"
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -200,8 +200,7 @@ int launch_bf16_pw(void* y, const void* x, const void* wpack, const float* bias,
 // weights, no per-sample output scale, no accumulation; Cin 32 / 64 / 128, Cout % 8 == 0 up to 256, 16-byte aligned y.
 // IDEAS_BF16_PW=0: never (A/B; read per call).
 int ideas_bf16_pw_ok(const ideas_conv_params* p, int per_image, const float* out_scale, const void* y, const void* resid) {
-    const char* e = getenv("IDEAS_BF16_PW");
-    if (e && e[0] == '0') return 0;
+    if (ideas_env_off("IDEAS_BF16_PW")) return 0;
     if (per_image || out_scale || p->accumulate || p->reflect) return 0;
     if (p->TY != 1 || p->TX != 1 || p->sy != 1 || p->sx != 1 || p->offy != 0 || p->offx != 0) return 0;
     if (p->osy != 1 || p->osx != 1 || p->ooy != 0 || p->oox != 0) return 0;

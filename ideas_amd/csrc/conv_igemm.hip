@@ -24,7 +24,7 @@
 // so ids are remapped to give each XCD (= each private L2) one contiguous band of M tiles with all its N
 // tiles; 3x3 halos and the N-tile re-reads of the same activations then hit that XCD's L2.
 #include "conv_epilogue.hpp"
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -453,8 +453,8 @@ int launch_fwd_cfg(void* y, const void* x, const void* wmat, const float* in_sca
     const int64_t M = (int64_t)p->B * p->OH * p->OW;
     const int64_t tm = ideas_cdiv(M, BM_);
     const int tn = (int)ideas_cdiv(p->Cout, BN_);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    auto go = [&](auto sc, auto rf) {
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) {
         if (p->Cin >= BK)
             hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value, true>),
                                dim3((unsigned)(tm * tn)), dim3(256), 0, stream, (float*)y, (const float*)x,
@@ -463,74 +463,40 @@ int launch_fwd_cfg(void* y, const void* x, const void* wmat, const float* in_sca
             hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value, false>),
                                dim3((unsigned)(tm * tn)), dim3(256), 0, stream, (float*)y, (const float*)x,
                                (const float*)wmat, in_scale, out_scale, bias, (const float*)resid, *p, tn);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    });
     return ideas_launch_status();
 }
 
-template <int WM, int WN, int MT, int NT>
+template <typename T> int64_t wgrad_slots(bool sc) {
+    return (int64_t)ideas_cu_count() * (sc ? ideas_blocks_per_cu<conv_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, true, false, true>>(256)
+                                           : ideas_blocks_per_cu<conv_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, false, false, true>>(256));
+}
+
+// split-K plan: pixels in steps of BK, >= 16 steps per block, plain two-wave target, whole waves
+SplitK wgrad_plan(const ideas_conv_params* p, int BM_, int BN_, int64_t slots) {
+    const int64_t P = (int64_t)p->B * p->OH * p->OW;
+    const int64_t tiles = ideas_cdiv(p->Cout, BM_) * ideas_cdiv(p->TY * p->TX * p->Cin, BN_);
+    const int64_t splits = std::min({splitk_target(slots, tiles, P, 0), ideas_cdiv(P, 16 * BK), (int64_t)65535});
+    return splitk_whole_waves(splitk_round(P, splits, BK), P, BK, tiles, slots);
+}
+
+template <typename T>
 int launch_wgrad_cfg(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale,
                      const ideas_conv_params* p, hipStream_t stream) {
-    constexpr int BM_ = WM * MT * 32, BN_ = WN * NT * 32;
-    const int64_t P = (int64_t)p->B * p->OH * p->OW;
-    const int Ktot = p->TY * p->TX * p->Cin;
-    const int tm = (int)ideas_cdiv(p->Cout, BM_);
-    const int tn = (int)ideas_cdiv(Ktot, BN_);
-    const int64_t tiles = (int64_t)tm * tn;
-    // split-K sizing: the grid should be a whole number of "waves" of resident blocks, otherwise the last,
-    // partially filled wave costs as much as a full one (1026 blocks on 1024 slots ran 2x the time).
-    const bool sc_ = in_scale && out_scale;
-    static int occ_cache[2] = {0, 0};
-    if (!occ_cache[sc_]) {
-        int occ = 0;
-        hipError_t e = sc_ ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_wgrad_kernel<WM, WN, MT, NT, true, false, true>, 256, 0)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_wgrad_kernel<WM, WN, MT, NT, false, false, true>, 256, 0);
-        occ_cache[sc_] = (e == hipSuccess && occ > 0) ? occ : 2;
-    }
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int64_t slots = (int64_t)occ_cache[sc_] * n_cu;
-    const int64_t max_splits = ideas_cdiv(P, 16 * BK);          // keep >= 16 pipeline steps per block
-    int64_t splits = (2 * slots) / tiles;                        // aim at two full waves of blocks
-    if (splits < 1) splits = 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 65535) splits = 65535;
-    int64_t per = ideas_cdiv(ideas_cdiv(P, splits), BK) * BK;
-    splits = ideas_cdiv(P, per);
-    // rounding `per` up to BK can shave a split off; re-balance so the block count stays a multiple of the slots
-    {
-        const int64_t blocks = tiles * splits;
-        const int64_t waves = blocks / slots;
-        if (waves >= 1 && blocks % slots) {
-            const int64_t want = (waves * slots) / tiles;        // largest split count giving whole waves
-            if (want >= 1) {
-                per = ideas_cdiv(ideas_cdiv(P, want), BK) * BK;
-                splits = ideas_cdiv(P, per);
-            }
-        }
-    }
-    auto go = [&](auto sc, auto rf) {
+    const int tm = (int)ideas_cdiv(p->Cout, T::BM);
+    const int tn = (int)ideas_cdiv(p->TY * p->TX * p->Cin, T::BN);
+    const bool sc = in_scale && out_scale;
+    const SplitK k = wgrad_plan(p, T::BM, T::BN, wgrad_slots<T>(sc));
+    with_flags(sc, p->reflect, [&](auto sc_, auto rf) {
         if (p->OW >= BK)
-            hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value, true>),
-                               dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, stream, gw, (const float*)gy,
-                               (const float*)x, in_scale, out_scale, *p, tn, per);
+            hipLaunchKernelGGL((conv_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, decltype(sc_)::value, decltype(rf)::value, true>),
+                               dim3((unsigned)(tm * tn), (unsigned)k.splits), dim3(256), 0, stream, gw, (const float*)gy,
+                               (const float*)x, in_scale, out_scale, *p, tn, k.per);
         else
-            hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, MT, NT, decltype(sc)::value, decltype(rf)::value, false>),
-                               dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, stream, gw, (const float*)gy,
-                               (const float*)x, in_scale, out_scale, *p, tn, per);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool sc = sc_;
-    if (sc) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+            hipLaunchKernelGGL((conv_wgrad_kernel<T::WM, T::WN, T::MT, T::NT, decltype(sc_)::value, decltype(rf)::value, false>),
+                               dim3((unsigned)(tm * tn), (unsigned)k.splits), dim3(256), 0, stream, gw, (const float*)gy,
+                               (const float*)x, in_scale, out_scale, *p, tn, k.per);
+    });
     return ideas_launch_status();
 }
 
@@ -610,7 +576,29 @@ extern "C" int ideas_conv_wgrad(float* gw, const void* gy, const void* x, const 
     if (dtype == IDEAS_F32_B3 && ideas_b3_wgrad3_enabled() && ideas_b3_wgrad3_supported(p))
         return ideas_b3_wgrad3(gw, gy, x, in_scale, out_scale, p, stream);      // 3x3: tap-fused, rolling window (conv_b3_wgrad3.hip)
     if (dtype == IDEAS_F32_B3 && ideas_b3_wgrad_supported(p)) return ideas_b3_wgrad(gw, gy, x, in_scale, out_scale, p, stream);
-    if (p->Cout > 64) return launch_wgrad_cfg<2, 2, 2, 2>(gw, gy, x, in_scale, out_scale, p, stream);  // 128 (o) x 128 (k)
-    if (p->Cout > 32) return launch_wgrad_cfg<2, 2, 1, 2>(gw, gy, x, in_scale, out_scale, p, stream);  // 64 x 128
-    return launch_wgrad_cfg<1, 4, 1, 1>(gw, gy, x, in_scale, out_scale, p, stream);                    // 32 x 128
+    return ideas_wgrad_tile(p, [&](auto t) { return launch_wgrad_cfg<decltype(t)>(gw, gy, x, in_scale, out_scale, p, stream); });
+}
+
+static ideas_plan igemm_wgrad_plan(const ideas_conv_params* p, int sc, int64_t slots) {
+    SplitK k;
+    ideas_wgrad_tile(p, [&](auto t) {
+        if (slots <= 0) slots = wgrad_slots<decltype(t)>(sc != 0);
+        k = wgrad_plan(p, t.BM, t.BN, slots);
+        return 0;
+    });
+    return {k, slots};
+}
+
+// What a split-K launcher would pass to its kernel for *p (the launchers call the same plan functions): out = {splits / ranges, units
+// per split, splits / parts per image or 0, slots}.  site: 0 this file, 1 conv_wino, 2 conv_b3_wgrad, 3 conv_b3_wgrad3, 4 conv_b3_pw,
+// 5 conv_bf16 (generic), 6 conv_bf16 (tap-fused).  No HIP call with slots > 0.  For tests and A/B scripts: a diagnostic that is not
+// part of the ABI of include/ideas_hip.h and not bound by ideas_amd/_lib.py.
+extern "C" int ideas_conv_splitk_plan(int site, const ideas_conv_params* p, int scaled, int64_t slots, int64_t* out) {
+    ideas_plan_query* const q[7] = {igemm_wgrad_plan,       ideas_wino_wgrad_plan, ideas_b3_wgrad_plan,   ideas_b3_wgrad3_plan,
+                                    ideas_b3_pw_wgrad_plan, ideas_bf16_wgrad_plan, ideas_bf16_wgrad3_plan};
+    if (!p || !out) return IDEAS_E_NULL;
+    if (site < 0 || site >= 7) return IDEAS_E_UNSUPPORTED;
+    const ideas_plan r = q[site](p, scaled, slots);
+    out[0] = r.k.splits; out[1] = r.k.per; out[2] = r.k.spi; out[3] = r.slots;
+    return IDEAS_OK;
 }

@@ -20,7 +20,7 @@
 // ((row>>3)&1) instead of padding -> conflict-free ds_read_b128, 48 KB double-buffered.  Same pipeline as
 // conv_igemm: one basic block per K-step, loads of step t+2 issued while step t computes.
 #include "conv_epilogue.hpp"
-#include <type_traits>
+#include "conv_launch.hpp"
 
 namespace {
 
@@ -418,17 +418,22 @@ extern "C" int ideas_conv3x3_wino(void* y, const void* x, const void* umat, cons
     const int64_t M = (int64_t)p->B * p->IH * (p->IW / 2);
     const int64_t tm = ideas_cdiv(M, WBM);
     const int tn = (int)ideas_cdiv(p->Cout, WBN);
-    if (tm * tn > 0x7fffffffLL) return IDEAS_E_SHAPE;
-    auto go = [&](auto sc, auto rf) {
+    if (!ideas_grid_fits(tm * tn)) return IDEAS_E_SHAPE;
+    with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) {
         hipLaunchKernelGGL((conv3x3_wino_kernel<decltype(sc)::value, decltype(rf)::value>), dim3((unsigned)(tm * tn)),
                            dim3(256), 0, stream, (float*)y, (const float*)x, (const float*)umat, in_scale, out_scale, bias,
                            (const float*)resid, *p, tn);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+    });
     return ideas_launch_status();
+}
+
+// split-K plan of the weight gradient: column pairs in steps of GBK, >= 16 steps per block, plain two-wave target, whole waves
+ideas_plan ideas_wino_wgrad_plan(const ideas_conv_params* p, int, int64_t slots) {
+    if (slots <= 0) slots = 2LL * ideas_cu_count();            // 2 blocks per CU (208 VGPRs): a constant, not queried
+    const int64_t P2 = (int64_t)p->B * p->IH * (p->IW / 2);
+    const int64_t tiles = ideas_cdiv(p->Cout, GBM) * ideas_cdiv(3 * p->Cin, GBN);
+    const int64_t splits = std::min({splitk_target(slots, tiles, P2, 0), ideas_cdiv(P2, 16 * GBK), (int64_t)65535});
+    return {splitk_whole_waves(splitk_round(P2, splits, GBK), P2, GBK, tiles, slots), slots};
 }
 
 // gu: ZEROED [4][Cout][3][Cin]; gy [B,H,W,Cout], x [B,H,W,Cin].  Same geometry restrictions as ideas_conv3x3_wino,
@@ -448,44 +453,18 @@ extern "C" int ideas_conv3x3_wino_wgrad(float* gu, const void* gy, const void* x
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t P2 = (int64_t)p->B * p->IH * (p->IW / 2);
     if (P2 >= 0x7fffffffLL) return IDEAS_E_SHAPE;
-    const int Ktot = 3 * p->Cin;
-    const int tm = (int)ideas_cdiv(p->Cout, GBM), tn = (int)ideas_cdiv(Ktot, GBN);
-    const int64_t tiles = (int64_t)tm * tn;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int64_t slots = 2LL * n_cu;                       // 2 blocks per CU (208 VGPRs)
-    const int64_t max_splits = ideas_cdiv(P2, 16 * GBK);
-    int64_t splits = (2 * slots) / tiles;
-    if (splits < 1) splits = 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 65535) splits = 65535;
-    int64_t per = ideas_cdiv(ideas_cdiv(P2, splits), GBK) * GBK;
-    splits = ideas_cdiv(P2, per);
-    {
-        const int64_t blocks = tiles * splits, waves = blocks / slots;
-        if (waves >= 1 && blocks % slots) {
-            const int64_t want = (waves * slots) / tiles;
-            if (want >= 1) { per = ideas_cdiv(ideas_cdiv(P2, want), GBK) * GBK; splits = ideas_cdiv(P2, per); }
-        }
-    }
-    auto go = [&](auto sc, auto rf) {
+    const int tiles = (int)(ideas_cdiv(p->Cout, GBM) * ideas_cdiv(3 * p->Cin, GBN)), tn = (int)ideas_cdiv(3 * p->Cin, GBN);
+    const SplitK k = ideas_wino_wgrad_plan(p, 0, 0).k;
+    with_flags(in_scale != nullptr, p->reflect, [&](auto sc, auto rf) {
         if (p->IW / 2 >= GBK)
             hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<decltype(sc)::value, decltype(rf)::value, true>),
-                               dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, stream, gu, (const float*)gy,
-                               (const float*)x, in_scale, out_scale, *p, tn, per);
+                               dim3((unsigned)tiles, (unsigned)k.splits), dim3(256), 0, stream, gu, (const float*)gy,
+                               (const float*)x, in_scale, out_scale, *p, tn, k.per);
         else
             hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<decltype(sc)::value, decltype(rf)::value, false>),
-                               dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, stream, gu, (const float*)gy,
-                               (const float*)x, in_scale, out_scale, *p, tn, per);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (in_scale) { if (p->reflect) go(T{}, T{}); else go(T{}, F{}); }
-    else { if (p->reflect) go(F{}, T{}); else go(F{}, F{}); }
+                               dim3((unsigned)tiles, (unsigned)k.splits), dim3(256), 0, stream, gu, (const float*)gy,
+                               (const float*)x, in_scale, out_scale, *p, tn, k.per);
+    });
     return ideas_launch_status();
 }
 

@@ -21,7 +21,8 @@
  *     n replaces the default tile-count rule by "at least n tiles of 64 x 256" (1: wherever Cout allows).  A diagnostic query beside this ABI, defined next to the
  *     dispatch in csrc/conv_b3_wino.hip, tells tests and A/B scripts which tile a forward of a given shape takes.)
  *     What IS memoised per process: immutable device properties (the CU count and the occupancy hipOccupancy... reports for the
- *     library's own split-K kernels), used to size grids;
+ *     library's own split-K kernels), used to size grids -- in one place, csrc/conv_launch.hpp (ideas_cu_count,
+ *     ideas_blocks_per_cu), each initialised once and thread-safely;
  *   - return value: 0 = enqueued; negative = argument error (IDEAS_E_*); positive = hipError_t of the launch.
  *
  * Layouts.  IDEAS_NCHW is the reference's layout (bias index (i / inner) % C,

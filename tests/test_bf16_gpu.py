@@ -202,6 +202,33 @@ def test_tiny_spatial_weight_gradient_vs_f64(case):
         assert rel_err(got2, ref2) < 2e-5, (case, "in-kernel scales", rel_err(got2, ref2))
 
 
+def test_bf16_tap_fused_weight_gradient_partial_last_part(monkeypatch):
+    """conv_bf16_wgrad3_kernel where an image's rows do NOT divide into its parts: 512 -> 512 at 104 x 128, B = 2 is the smallest
+    shape the dispatch gives to the tap-fused kernel (>= 6e9 products) with several parts -- three of 35 rows, the last one 34.
+    Against f64 on the same bf16 operands within the bound of test_tiny_spatial_weight_gradient_vs_f64 (f32 accumulation of exact
+    bf16 products), and against the generic kernel as in the full-size test below."""
+    import ideas_amd.op.conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom
+    torch.manual_seed(11)
+    B, C, H, W = 2, 512, 104, 128
+    g = ConvGeom(3, 3, 1, 1, False)
+    x = torch.randn(B, C, H, W, device="cuda").to(BF).contiguous(memory_format=CL)
+    gy = torch.randn(B, C, H, W, device="cuda").to(BF).contiguous(memory_format=CL)
+    gain = 1 / math.sqrt(C * 9)
+    out = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("IDEAS_BF16_WGRAD3", flag)
+        out[flag] = CV.conv_wgrad_raw(gy, x, g, (C, C, 3, 3), gain)
+    xp = F.pad(x.double(), [1] * 4)
+    gyd = gy.double().reshape(B, C, H * W)
+    ref = torch.stack([torch.stack([torch.einsum("bop,bip->oi", gyd, xp[:, :, ty:ty + H, tx:tx + W].reshape(B, C, H * W))
+                                    for tx in range(3)], -1) for ty in range(3)], -2) * gain
+    assert rel_err(out["1"], ref) < 2e-5 and rel_err(out["0"], ref) < 2e-5, (rel_err(out["1"], ref), rel_err(out["0"], ref))
+    scale = float(out["0"].abs().max())
+    assert float((out["1"] - out["0"]).abs().max()) <= 1e-4 * scale
+    assert float((out["1"] - out["0"]).abs().mean()) <= 1e-6 * scale
+
+
 def test_bf16_image_and_tap_fused_kernels_full_size(monkeypatch):
     """BASELINE-size check of the round-3 bf16 kernels on G.layers.7.conv2's shape (modulated 128 -> 128 at 256x256, B = 4): the LDS
     image kernel (forward, input gradient) and the tap-fused weight gradient against the generic kernels they replace on the same

@@ -78,6 +78,44 @@ def test_c_abi_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.ConvParams) == _lib.load().ideas_sizeof_conv_params() == 28 * 4
 
 
+def splitk_plan_rows(lib, cases, site, scaled, slots=None):
+    """ideas_conv_splitk_plan (the diagnostic beside the ABI, csrc/conv_igemm.hip) over rows of (B, OH, OW, Cin, Cout, taps, slots):
+    what the split-K launcher `site` would pass to its kernel.  `slots` overrides the column (0 = the launcher's own count)."""
+    import numpy as np
+    from ideas_amd import _lib
+    fn = lib.ideas_conv_splitk_plan
+    fn.argtypes = [ctypes.c_int, ctypes.POINTER(_lib.ConvParams), ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    fn.restype = ctypes.c_int
+    rows = np.zeros((len(cases), 4), dtype=np.int64)
+    out = (ctypes.c_int64 * 4)()
+    for i, (B, OH, OW, Cin, Cout, K, s) in enumerate(cases):
+        p = _lib.ConvParams(B=B, IH=OH, IW=OW, Cin=Cin, YH=OH, YW=OW, Cout=Cout, OH=OH, OW=OW, TY=K, TX=K, sy=1, sx=1, dy=1, dx=1,
+                            offy=-(K // 2), offx=-(K // 2), osy=1, osx=1)
+        assert fn(site, ctypes.byref(p), scaled, s if slots is None else slots, out) == 0
+        rows[i] = out[:]
+    return rows
+
+
+def test_splitk_plans_match_pinned():
+    """Every split-K launcher sizes its grid as the commit before the launch rules were consolidated did: the library's plan query over
+    the sweep of tests/golden/make_golden_splitk_plans.py (a transcription of that commit's arithmetic) against its digests."""
+    import hashlib
+    import numpy as np
+    from ideas_amd import _lib
+    g = np.load(os.path.join(GOLDEN, "splitk_plans.npz"))
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    cases = g["cases"].astype(np.int64)
+    names = sorted(k[:-5] for k in g.files if k.endswith("/site"))
+    assert len(names) == 8
+    for name in names:
+        site, scaled = (int(v) for v in g[name + "/site"])
+        sel = cases[g[name + "/idx"]].tolist()
+        assert len(sel) == int(g[name + "/n"]) > 1000, name
+        rows = splitk_plan_rows(lib, sel, site, scaled)
+        assert (rows[:16] == g[name + "/head"]).all(), (name, rows[:16], g[name + "/head"])
+        assert hashlib.sha256(rows.tobytes()).digest() == bytes(g[name + "/sha256"]), name
+
+
 def test_ops_fail_loudly_on_cpu_tensors():
     import ideas_amd.op as op
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -752,6 +752,8 @@ B3_CASES = [
     # the row-sharing patch kernel (conv_b3_wino2d_kernel): 2 x 32, 4 x 16 and 8 x 8 patches, mirror padding, modulation, two N tiles
     (2, 32, 128, 8, 64, 3, 1, 1, True, False), (1, 64, 96, 6, 128, 3, 1, 1, False, True), (2, 32, 160, 16, 32, 3, 1, 1, True, True),
     (3, 32, 200, 8, 16, 3, 1, 1, False, False),
+    # conv_b3_wgrad_kernel with five splits of 240 pixels, the last one partial (1152 pixels)
+    (3, 256, 72, 24, 16, 3, 1, 1, False, False),
 ]
 
 
@@ -952,6 +954,7 @@ WGRAD3_CASES = [
     (1, 64, 64, 64, 48, 2, False, False),      # stride 2: three strips, ranges cut inside the image
     (3, 64, 128, 16, 32, 2, False, True),      # stride 2, modulated, three images per range (scales and window change together)
     (2, 64, 64, 16, 16, 2, True, False),       # stride 2 with one pixel of mirror padding (input 2H-1)
+    (3, 64, 64, 28, 16, 1, False, False),      # five ranges of 17 rows, the last one partial (84 rows)
 ]
 
 
@@ -1120,6 +1123,7 @@ WINO_WGRAD_CASES = [
     # B, Cin, Cout, H, W, reflect, scaled
     (2, 32, 64, 64, 256, False, False), (2, 64, 128, 32, 64, False, True), (1, 128, 72, 32, 64, False, False), (4, 32, 64, 64, 128, True, False),
     (8, 16, 40, 64, 16, False, True),
+    (3, 32, 64, 18, 16, False, False),      # four splits of 112 column pairs, the last one partial (432 pairs)
 ]
 
 

@@ -15,14 +15,13 @@
 // f32 or bf16 tensors (f32 arithmetic, one rounding at the store), NCHW or NHWC.
 //
 // Work split.  NCHW: one thread per output pixel, looping over c -- the taps and weights are computed once a pixel and a wave
-// stores 64 consecutive elements of a plane.  NHWC with C % 4 == 0 (f32; % 8 for bf16) and 16-byte aligned tensors: one thread
-// per (pixel, 16-byte vector of channels); any other C: one thread per (pixel, channel) element.  Consecutive threads take
-// consecutive addresses of y in every case.
+// stores 64 consecutive elements of a plane.  NHWC: one thread per (pixel, channel vector of VW elements by the rule of
+// stream.hpp).  Consecutive threads take consecutive addresses of y in every case.
 //
 // Out-of-range safety.  A position is used only if it lies in (-1, W) x (-1, H) -- a comparison that is false for NaN -- and
 // the sample's six theta values are all finite; otherwise the four weights are zero.  The tap indices are clamped into the image
 // BEFORE any address is formed, whatever theta holds.
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -59,30 +58,6 @@ __device__ __forceinline__ WarpTaps warp_taps(const float* __restrict__ th, int 
 __device__ __forceinline__ float warp_blend(const WarpTaps& t, float a, float b, float c, float d) {
     return t.w00 * a + t.w01 * b + t.w10 * c + t.w11 * d;
 }
-
-// VW consecutive elements <-> f32: one 16-byte access for (float, 4) and (bf16, 8), an element access for VW = 1
-template <typename T, int VW> struct aug_io;
-template <typename T> struct aug_io<T, 1> {
-    static __device__ __forceinline__ void load(const T* p, float (&f)[1]) { f[0] = ld1(p); }
-    static __device__ __forceinline__ void store(T* p, const float (&f)[1]) { st1(p, f[0]); }
-};
-template <> struct aug_io<float, 4> {
-    static __device__ __forceinline__ void load(const float* p, float (&f)[4]) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&f)[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    }
-};
-template <> struct aug_io<ideas_bf16, 8> {
-    static __device__ __forceinline__ void load(const ideas_bf16* p, float (&f)[8]) {
-        unpack8(*reinterpret_cast<const uint4*>(p), f, ideas_bf16{});
-    }
-    static __device__ __forceinline__ void store(ideas_bf16* p, const float (&f)[8]) {
-        *reinterpret_cast<uint4*>(p) = pack8(f, ideas_bf16{});
-    }
-};
 
 struct WarpArgs {
     int B, C, H, W, OH, OW;
@@ -150,13 +125,13 @@ __global__ __launch_bounds__(256) void warp_nhwc_kernel(T* __restrict__ y, const
     const WarpTaps t = warp_taps(theta + (int64_t)b * 6, ox, oy, a.H, a.W);
     const T* xp = x + (int64_t)b * a.H * a.W * a.C + (int64_t)v * VW;
     float p00[VW], p01[VW], p10[VW], p11[VW], o[VW];
-    aug_io<T, VW>::load(xp + ((int64_t)t.y0 * a.W + t.x0) * a.C, p00);
-    aug_io<T, VW>::load(xp + ((int64_t)t.y0 * a.W + t.x1) * a.C, p01);
-    aug_io<T, VW>::load(xp + ((int64_t)t.y1 * a.W + t.x0) * a.C, p10);
-    aug_io<T, VW>::load(xp + ((int64_t)t.y1 * a.W + t.x1) * a.C, p11);
+    chan_io<T, VW>::load(xp + ((int64_t)t.y0 * a.W + t.x0) * a.C, p00);
+    chan_io<T, VW>::load(xp + ((int64_t)t.y0 * a.W + t.x1) * a.C, p01);
+    chan_io<T, VW>::load(xp + ((int64_t)t.y1 * a.W + t.x0) * a.C, p10);
+    chan_io<T, VW>::load(xp + ((int64_t)t.y1 * a.W + t.x1) * a.C, p11);
 #pragma unroll
     for (int e = 0; e < VW; ++e) o[e] = warp_blend(t, p00[e], p01[e], p10[e], p11[e]);
-    aug_io<T, VW>::store(y + i * VW, o);            // (pixel * L + v) * VW = pixel * C + v * VW
+    chan_io<T, VW>::store(y + i * VW, o);            // (pixel * L + v) * VW = pixel * C + v * VW
 }
 
 template <typename T, int VW>
@@ -170,7 +145,7 @@ __global__ __launch_bounds__(256) void warp_bwd_nhwc_kernel(float* __restrict__ 
     const WarpTaps t = warp_taps(theta + (int64_t)b * 6, ox, oy, a.H, a.W);
     float* gp = gx + (int64_t)b * a.H * a.W * a.C + (int64_t)v * VW;
     float g[VW];
-    aug_io<T, VW>::load(gy + i * VW, g);
+    chan_io<T, VW>::load(gy + i * VW, g);
     float* q00 = gp + ((int64_t)t.y0 * a.W + t.x0) * a.C;
     float* q01 = gp + ((int64_t)t.y0 * a.W + t.x1) * a.C;
     float* q10 = gp + ((int64_t)t.y1 * a.W + t.x0) * a.C;
@@ -210,8 +185,7 @@ int warp_check(int B, int C, int H, int W, int OH, int OW, int layout, int dtype
 
 // geometry of a launch; vw: the channel vector of the NHWC kernels (1 on NCHW)
 WarpArgs warp_args(int B, int C, int H, int W, int OH, int OW, int layout, int dtype, bool aligned, int* vw) {
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    *vw = (layout == IDEAS_NHWC && aligned && C % w == 0) ? w : 1;
+    *vw = ideas_chan_vw(dtype, C, layout == IDEAS_NHWC && aligned);
     WarpArgs a;
     a.B = B; a.C = C; a.H = H; a.W = W; a.OH = OH; a.OW = OW;
     a.L = layout == IDEAS_NHWC ? C / *vw : 1;
@@ -229,15 +203,11 @@ extern "C" int ideas_affine_warp(void* y, const void* x, const float* theta, int
     const WarpArgs a = warp_args(B, C, H, W, OH, OW, layout, dtype, ideas_aligned16(y) && ideas_aligned16(x), &vw);
     const dim3 grid((unsigned)ideas_cdiv(a.n, 256)), block(256);
     hipStream_t s = (hipStream_t)stream_;
-#define GO(K, T) hipLaunchKernelGGL((K), grid, block, 0, s, (T*)y, (const T*)x, theta, a)
-    if (layout == IDEAS_NCHW) {
-        if (dtype == IDEAS_BF16) GO(warp_nchw_kernel<ideas_bf16>, ideas_bf16); else GO(warp_nchw_kernel<float>, float);
-    } else if (dtype == IDEAS_BF16) {
-        if (vw == 8) GO((warp_nhwc_kernel<ideas_bf16, 8>), ideas_bf16); else GO((warp_nhwc_kernel<ideas_bf16, 1>), ideas_bf16);
-    } else {
-        if (vw == 4) GO((warp_nhwc_kernel<float, 4>), float); else GO((warp_nhwc_kernel<float, 1>), float);
-    }
-#undef GO
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = layout == IDEAS_NCHW ? warp_nchw_kernel<T> : warp_nhwc_kernel<T, c.VW>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, (T*)y, (const T*)x, theta, a);
+    });
     return ideas_launch_status();
 }
 
@@ -253,15 +223,11 @@ extern "C" int ideas_affine_warp_bwd(float* gx, const void* gy, const float* the
     int vw;
     const WarpArgs a = warp_args(B, C, H, W, OH, OW, layout, dtype, ideas_aligned16(gy), &vw);
     const dim3 grid((unsigned)ideas_cdiv(a.n, 256)), block(256);
-#define GO(K, T) hipLaunchKernelGGL((K), grid, block, 0, s, gx, (const T*)gy, theta, a)
-    if (layout == IDEAS_NCHW) {
-        if (dtype == IDEAS_BF16) GO(warp_bwd_nchw_kernel<ideas_bf16>, ideas_bf16); else GO(warp_bwd_nchw_kernel<float>, float);
-    } else if (dtype == IDEAS_BF16) {
-        if (vw == 8) GO((warp_bwd_nhwc_kernel<ideas_bf16, 8>), ideas_bf16); else GO((warp_bwd_nhwc_kernel<ideas_bf16, 1>), ideas_bf16);
-    } else {
-        if (vw == 4) GO((warp_bwd_nhwc_kernel<float, 4>), float); else GO((warp_bwd_nhwc_kernel<float, 1>), float);
-    }
-#undef GO
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = layout == IDEAS_NCHW ? warp_bwd_nchw_kernel<T> : warp_bwd_nhwc_kernel<T, c.VW>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, gx, (const T*)gy, theta, a);
+    });
     return ideas_launch_status();
 }
 
@@ -273,9 +239,10 @@ extern "C" int ideas_color_affine(void* y, const void* x, const float* m, int B,
     const int64_t P = (int64_t)H * W, n = (int64_t)B * P;
     const dim3 grid((unsigned)ideas_cdiv(n, 256)), block(256);
     hipStream_t s = (hipStream_t)stream_;
-#define GO(T, L) hipLaunchKernelGGL((color_affine_kernel<T, L>), grid, block, 0, s, (T*)y, (const T*)x, m, P, n)
-    if (dtype == IDEAS_BF16) { if (layout == IDEAS_NHWC) GO(ideas_bf16, true); else GO(ideas_bf16, false); }
-    else { if (layout == IDEAS_NHWC) GO(float, true); else GO(float, false); }
-#undef GO
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = layout == IDEAS_NHWC ? color_affine_kernel<T, true> : color_affine_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, (T*)y, (const T*)x, m, P, n);
+    });
     return ideas_launch_status();
 }

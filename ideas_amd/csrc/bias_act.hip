@@ -5,7 +5,7 @@
 // 16-byte coalesced traffic.  NHWC keeps a thread's four lanes on four fixed channels for the whole
 // grid-stride loop, which lets the bias gradient be reduced in registers -> LDS -> one atomic per channel per
 // block instead of the reference's second full pass (fused_act.py:33-38).
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -324,9 +324,9 @@ extern "C" int ideas_channel_sum(float* out, const void* x, int64_t n, int C, in
     const int m = C / gcd_i(C, 256);                         // 256 * grid must be a multiple of C
     grid = ideas_cdiv(grid, m) * m;
     const size_t lds = (size_t)C * sizeof(float);
-    if (dtype == IDEAS_BF16)
-        hipLaunchKernelGGL(channel_sum_nhwc_kernel<ideas_bf16>, dim3((unsigned)grid), dim3(256), lds, stream, out, (const ideas_bf16*)x, n, C);
-    else
-        hipLaunchKernelGGL(channel_sum_nhwc_kernel<float>, dim3((unsigned)grid), dim3(256), lds, stream, out, (const float*)x, n, C);
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL(channel_sum_nhwc_kernel<T>, dim3((unsigned)grid), dim3(256), lds, stream, out, (const T*)x, n, C);
+    });
     return ideas_launch_status();
 }

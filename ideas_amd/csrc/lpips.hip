@@ -13,49 +13,23 @@
 //                   A pixel with n_i = 0 gets gf_i = 0 (the reference's sqrt backward gives NaN there), see DESIGN.md 3.13.
 //
 // Tensors are channels-innermost [B, H, W, C] in f32 or bf16, arithmetic is f32 (the sum over pixels is double), one rounding at
-// the store; w, gd and d are f32.  16-byte vectors along C when C % VW == 0 (VW = 4 f32 / 8 bf16) and every pointer is 16-byte
-// aligned, an element path (VW = 1) for any other C or alignment: the rule of noise_act.hip.
+// the store; w, gd and d are f32.  Channel vectors of VW elements by the rule of stream.hpp.
 //
-// Head work split (noise_act.hip's): a pixel is owned by a GROUP of G lanes, G = the power of two >= min(L, 64), L = C / VW; lane l
-// takes the vectors l, l + G, ... (at most KV of them, a template parameter) of BOTH tensors and keeps them in registers, so each
-// tensor is read from HBM once: the two norms, then the weighted sum (the dot products in the backward), are xor butterflies in
-// the group.  G divides 64: a group never straddles a wave; consecutive groups take consecutive pixels.
+// Head work split: a pixel is owned by a group of G = ideas_lane_group(C / VW) lanes; lane l takes the vectors l, l + G, ... (at
+// most KV of them, a template parameter) of BOTH tensors and keeps them in registers, so each tensor is read from HBM once: the
+// two norms, then the weighted sum (the dot products in the backward), are group_sum butterflies.  Consecutive groups take
+// consecutive pixels.
 //
-// d[b] without floating-point atomics (minibatch_stddev.hip's scheme): grid (nblk, B); lane 0 of a group adds its pixels in
-// double in index order, the wave combines with the xor butterfly, thread 0 adds the four waves in order and writes ONE double
-// per block and sample; a second small kernel adds the <= IDEAS_LPIPS_MAX_PARTIALS partials of a sample in index order and
-// applies 1/(HW).  The backward has no reduction across pixels.  Everything here is bitwise reproducible.
-#include "common.hpp"
+// d[b] without floating-point atomics: grid (nblk, B); lane 0 of a group adds its pixels in double in index order, block_sum_256
+// gives ONE double per block and sample; a second small kernel adds the <= IDEAS_LPIPS_MAX_PARTIALS partials of a sample in index
+// order and applies 1/(HW).  The backward has no reduction across pixels.  Everything here is bitwise reproducible.
+#include "stream.hpp"
 
 namespace {
 
 constexpr int LP_MAX_BLOCKS = IDEAS_LPIPS_MAX_PARTIALS;
 constexpr float LP_EPS = 1e-10f;
 constexpr int LP_MAX_LANE_ELEMS = 32;                     // elements of one tensor a lane holds: C <= 64 * 32
-
-// VW consecutive elements <-> f32: one 16-byte access for (float, 4) and (bf16, 8), an element access for VW = 1
-template <typename T, int VW> struct lp_io;
-template <typename T> struct lp_io<T, 1> {
-    static __device__ __forceinline__ void load(const T* p, float (&f)[1]) { f[0] = ld1(p); }
-    static __device__ __forceinline__ void store(T* p, const float (&f)[1]) { st1(p, f[0]); }
-};
-template <> struct lp_io<float, 4> {
-    static __device__ __forceinline__ void load(const float* p, float (&f)[4]) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&f)[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    }
-};
-template <> struct lp_io<ideas_bf16, 8> {
-    static __device__ __forceinline__ void load(const ideas_bf16* p, float (&f)[8]) {
-        unpack8(*reinterpret_cast<const uint4*>(p), f, ideas_bf16{});
-    }
-    static __device__ __forceinline__ void store(ideas_bf16* p, const float (&f)[8]) {
-        *reinterpret_cast<uint4*>(p) = pack8(f, ideas_bf16{});
-    }
-};
 
 // ---- 2x2 max pool ---------------------------------------------------------------------------------------------------------------
 struct PoolArgs {
@@ -79,10 +53,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(T* __restrict__ y, con
         // 2 oh + 1 < H and 2 ow + 1 < W: OH = H / 2, OW = W / 2
         const int64_t base = ((b * a.H + 2 * oh) * a.W + 2 * ow) * a.C + (int64_t)v * VW;
         float q[4][VW], m[VW];
-        lp_io<T, VW>::load(x + base, q[0]);
-        lp_io<T, VW>::load(x + base + a.C, q[1]);
-        lp_io<T, VW>::load(x + base + row, q[2]);
-        lp_io<T, VW>::load(x + base + row + a.C, q[3]);
+        chan_io<T, VW>::load(x + base, q[0]);
+        chan_io<T, VW>::load(x + base + a.C, q[1]);
+        chan_io<T, VW>::load(x + base + row, q[2]);
+        chan_io<T, VW>::load(x + base + row + a.C, q[3]);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             m[e] = q[0][e];
@@ -90,7 +64,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(T* __restrict__ y, con
             for (int k = 1; k < 4; ++k)
                 if (pool_takes(q[k][e], m[e])) m[e] = q[k][e];
         }
-        lp_io<T, VW>::store(y + ((b * a.OH + oh) * a.OW + ow) * a.C + (int64_t)v * VW, m);
+        chan_io<T, VW>::store(y + ((b * a.OH + oh) * a.OW + ow) * a.C + (int64_t)v * VW, m);
     }
 }
 
@@ -112,11 +86,11 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(T* __restrict__ gx, co
         float o[4][VW];
         if (eh < a.OH && ew < a.OW) {
             float q[4][VW], g[VW];
-            lp_io<T, VW>::load(x + base, q[0]);
-            lp_io<T, VW>::load(x + base + a.C, q[1]);
-            lp_io<T, VW>::load(x + base + row, q[2]);
-            lp_io<T, VW>::load(x + base + row + a.C, q[3]);
-            lp_io<T, VW>::load(gy + ((b * a.OH + eh) * a.OW + ew) * a.C + (int64_t)v * VW, g);
+            chan_io<T, VW>::load(x + base, q[0]);
+            chan_io<T, VW>::load(x + base + a.C, q[1]);
+            chan_io<T, VW>::load(x + base + row, q[2]);
+            chan_io<T, VW>::load(x + base + row + a.C, q[3]);
+            chan_io<T, VW>::load(gy + ((b * a.OH + eh) * a.OW + ew) * a.C + (int64_t)v * VW, g);
 #pragma unroll
             for (int e = 0; e < VW; ++e) {
                 float m = q[0][e];
@@ -127,18 +101,18 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(T* __restrict__ gx, co
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o[k][e] = (arg == k) ? g[e] : 0.f;
             }
-            lp_io<T, VW>::store(gx + base, o[0]);
-            lp_io<T, VW>::store(gx + base + a.C, o[1]);
-            lp_io<T, VW>::store(gx + base + row, o[2]);
-            lp_io<T, VW>::store(gx + base + row + a.C, o[3]);
+            chan_io<T, VW>::store(gx + base, o[0]);
+            chan_io<T, VW>::store(gx + base + a.C, o[1]);
+            chan_io<T, VW>::store(gx + base + row, o[2]);
+            chan_io<T, VW>::store(gx + base + row + a.C, o[3]);
         } else {
 #pragma unroll
             for (int e = 0; e < VW; ++e) o[0][e] = 0.f;
             const bool in_h = 2 * eh + 1 < a.H, in_w = 2 * ew + 1 < a.W;      // (2 eh < H and 2 ew < W by the grid)
-            lp_io<T, VW>::store(gx + base, o[0]);
-            if (in_w) lp_io<T, VW>::store(gx + base + a.C, o[0]);
-            if (in_h) lp_io<T, VW>::store(gx + base + row, o[0]);
-            if (in_h && in_w) lp_io<T, VW>::store(gx + base + row + a.C, o[0]);
+            chan_io<T, VW>::store(gx + base, o[0]);
+            if (in_w) chan_io<T, VW>::store(gx + base + a.C, o[0]);
+            if (in_h) chan_io<T, VW>::store(gx + base + row, o[0]);
+            if (in_h && in_w) chan_io<T, VW>::store(gx + base + row + a.C, o[0]);
         }
     }
 }
@@ -146,8 +120,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(T* __restrict__ gx, co
 int pool_check(int B, int C, int H, int W, int dtype, bool vec_aligned, PoolArgs* a, int* vw) {
     if (dtype != IDEAS_F32 && dtype != IDEAS_BF16) return IDEAS_E_UNSUPPORTED;
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return IDEAS_E_SHAPE;              // H / 2 and W / 2 must be positive
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    *vw = (vec_aligned && C % w == 0) ? w : 1;
+    *vw = ideas_chan_vw(dtype, C, vec_aligned);
     *a = PoolArgs{B, H, W, C, H / 2, W / 2, C / *vw};
     return IDEAS_OK;
 }
@@ -165,12 +138,6 @@ struct LpArgs {
     float inv_p;          // 1 / (H W)
 };
 
-// the sum over the G lanes of a group (G a power of two <= 64), the same value in each of them; every lane of the wave calls it
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the lane's vectors l, l + G, ... of one pixel (zeros past L, and for a pixel past the end)
 template <typename T, int VW, int KV>
 __device__ __forceinline__ void lp_load(const T* __restrict__ f, int l, int G, int L, bool live, float (&r)[KV][VW]) {
@@ -178,7 +145,7 @@ __device__ __forceinline__ void lp_load(const T* __restrict__ f, int l, int G, i
     for (int k = 0; k < KV; ++k) {
         const int v = l + k * G;
         if (live && v < L) {
-            lp_io<T, VW>::load(f + (int64_t)v * VW, r[k]);
+            chan_io<T, VW>::load(f + (int64_t)v * VW, r[k]);
         } else {
 #pragma unroll
             for (int e = 0; e < VW; ++e) r[k][e] = 0.f;
@@ -262,10 +229,8 @@ __global__ __launch_bounds__(256) void lpips_fwd_kernel(double* __restrict__ par
             if (l == 0) acc += (double)s;                  // (zero for a pixel past the end)
         }
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+    acc = block_sum_256<double, true>(acc, s_part);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
 // d[b] = (1/(HW)) * the sum, in index order, of the sample's partials
@@ -329,12 +294,12 @@ __global__ __launch_bounds__(256) void lpips_bwd_kernel(T* __restrict__ gf0, T* 
                 if (gf0) {
 #pragma unroll
                     for (int e = 0; e < VW; ++e) o[e] = g[k][e] * z0 - x0[u][k][e] * c0;
-                    lp_io<T, VW>::store(gf0 + pix * a.C + (int64_t)v * VW, o);
+                    chan_io<T, VW>::store(gf0 + pix * a.C + (int64_t)v * VW, o);
                 }
                 if (gf1) {
 #pragma unroll
                     for (int e = 0; e < VW; ++e) o[e] = x1[u][k][e] * c1 - g[k][e] * z1;
-                    lp_io<T, VW>::store(gf1 + pix * a.C + (int64_t)v * VW, o);
+                    chan_io<T, VW>::store(gf1 + pix * a.C + (int64_t)v * VW, o);
                 }
             }
         }
@@ -346,17 +311,13 @@ int lp_check(int B, int C, int H, int W, int dtype, bool vec_aligned, LpArgs* a,
     if (dtype != IDEAS_F32 && dtype != IDEAS_BF16) return IDEAS_E_UNSUPPORTED;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffLL || B > 65535) return IDEAS_E_SHAPE;
     if (C > 64 * LP_MAX_LANE_ELEMS) return IDEAS_E_UNSUPPORTED;                 // a pixel of both tensors lives in registers
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    *vw = (vec_aligned && C % w == 0) ? w : 1;
-    const int L = C / *vw;
-    int G = 1;
-    while (G < L && G < 64) G <<= 1;
-    *kv = (L + G - 1) / G;
+    *vw = ideas_chan_vw(dtype, C, vec_aligned);
     a->P = (int64_t)H * W;
     a->B = B;
     a->C = C;
-    a->L = L;
-    a->G = G;
+    a->L = C / *vw;
+    a->G = ideas_lane_group(a->L);
+    *kv = (a->L + a->G - 1) / a->G;
     a->inv_p = (float)(1.0 / (double)a->P);
     return IDEAS_OK;
 }
@@ -385,13 +346,6 @@ void lp_bwd_launch(int kv, dim3 grid, hipStream_t stream, void* gf0, void* gf1, 
 }
 #undef LP_PICK_KV
 
-// FN<T, VW>(...) for the storage dtype and the vector width lp_check chose
-#define LP_LAUNCH(FN, ...)                                                                                                         \
-    do {                                                                                                                           \
-        if (dtype == IDEAS_BF16) { if (vw == 8) FN<ideas_bf16, 8>(__VA_ARGS__); else FN<ideas_bf16, 1>(__VA_ARGS__); }             \
-        else { if (vw == 4) FN<float, 4>(__VA_ARGS__); else FN<float, 1>(__VA_ARGS__); }                                           \
-    } while (0)
-
 }  // namespace
 
 extern "C" int ideas_maxpool2x2_fwd(void* y, const void* x, int B, int C, int H, int W, int dtype, void* stream_) {
@@ -402,10 +356,10 @@ extern "C" int ideas_maxpool2x2_fwd(void* y, const void* x, int B, int C, int H,
     if (!y || !x) return IDEAS_E_NULL;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid(pool_grid((int64_t)B * a.OH * a.OW * a.L));
-#define POOL_FWD(T, VW) hipLaunchKernelGGL((maxpool_fwd_kernel<T, VW>), grid, dim3(256), 0, stream, (T*)y, (const T*)x, a)
-    if (dtype == IDEAS_BF16) { if (vw == 8) POOL_FWD(ideas_bf16, 8); else POOL_FWD(ideas_bf16, 1); }
-    else { if (vw == 4) POOL_FWD(float, 4); else POOL_FWD(float, 1); }
-#undef POOL_FWD
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((maxpool_fwd_kernel<T, c.VW>), grid, dim3(256), 0, stream, (T*)y, (const T*)x, a);
+    });
     return ideas_launch_status();
 }
 
@@ -417,10 +371,10 @@ extern "C" int ideas_maxpool2x2_bwd(void* gx, const void* gy, const void* x, int
     if (!gx || !gy || !x) return IDEAS_E_NULL;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid(pool_grid((int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) * a.L));
-#define POOL_BWD(T, VW) hipLaunchKernelGGL((maxpool_bwd_kernel<T, VW>), grid, dim3(256), 0, stream, (T*)gx, (const T*)gy, (const T*)x, a)
-    if (dtype == IDEAS_BF16) { if (vw == 8) POOL_BWD(ideas_bf16, 8); else POOL_BWD(ideas_bf16, 1); }
-    else { if (vw == 4) POOL_BWD(float, 4); else POOL_BWD(float, 1); }
-#undef POOL_BWD
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((maxpool_bwd_kernel<T, c.VW>), grid, dim3(256), 0, stream, (T*)gx, (const T*)gy, (const T*)x, a);
+    });
     return ideas_launch_status();
 }
 
@@ -436,7 +390,7 @@ extern "C" int ideas_lpips_layer_fwd(float* d, void* workspace, const void* f0, 
     int64_t nblk = ideas_cdiv(a.P, 256 / a.G);
     if (nblk > LP_MAX_BLOCKS) nblk = LP_MAX_BLOCKS;
     const dim3 grid((unsigned)nblk, (unsigned)B);
-    LP_LAUNCH(lp_fwd_launch, kv, grid, stream, part, f0, f1, w, a);
+    with_chan(dtype, vw, [&](auto c) { lp_fwd_launch<typename decltype(c)::type, c.VW>(kv, grid, stream, part, f0, f1, w, a); });
     const int st = ideas_launch_status();
     if (st) return st;
     hipLaunchKernelGGL(lpips_fill_kernel, dim3((unsigned)ideas_cdiv(B, 256)), dim3(256), 0, stream, d, part, B, (int)nblk, 1.0 / (double)a.P);
@@ -456,6 +410,6 @@ extern "C" int ideas_lpips_layer_bwd(void* gf0, void* gf1, const float* gd, cons
     int64_t nblk = ideas_cdiv((int64_t)B * a.P, 256 / a.G);
     if (nblk > 4096) nblk = 4096;
     const dim3 grid((unsigned)nblk);
-    LP_LAUNCH(lp_bwd_launch, kv, grid, stream, gf0, gf1, gd, f0, f1, w, a);
+    with_chan(dtype, vw, [&](auto c) { lp_bwd_launch<typename decltype(c)::type, c.VW>(kv, grid, stream, gf0, gf1, gd, f0, f1, w, a); });
     return ideas_launch_status();
 }

@@ -15,7 +15,7 @@
 //
 // Alignment.  A pixel of `out` / `gout` is C + feat elements: rows are not 16-byte aligned for C = 512 f32 (513 * 4 bytes) nor for
 // any bf16 case, so every access here is a scalar element access (a wave still covers 256 contiguous bytes of a pixel row).
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -25,15 +25,6 @@ struct MbArgs {
     int G, M, P, C, feat, nblk;
     float eps;
 };
-
-// block-wide sum with a fixed association; the result is valid in EVERY thread
-__device__ __forceinline__ double block_sum_256(double v, double* s_part) {
-    v = wave_sum(v);
-    __syncthreads();                       // s_part may still be read from a previous call
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-}
 
 // the G values of one column: loads (sample g at x[base + g * gstride]), mean, centred values u (two-pass) and sd -- in DOUBLE.
 // The backward of the backward is a difference of two terms in 1 / sd and u^2 / sd^3 that cancel down to eps / sd^2 of either
@@ -251,8 +242,7 @@ extern "C" int ideas_mbstd_fwd(void* out, void* workspace, const void* x, int B,
     if (rc) return rc;
     if (!out || !workspace || !x) return IDEAS_E_NULL;
     a.eps = eps;
-    return dtype == IDEAS_BF16 ? mb_fwd<ideas_bf16>(out, (double*)workspace, x, B, a, (hipStream_t)stream_)
-                               : mb_fwd<float>(out, (double*)workspace, x, B, a, (hipStream_t)stream_);
+    return with_dtype(dtype, [&](auto c) { return mb_fwd<typename decltype(c)::type>(out, (double*)workspace, x, B, a, (hipStream_t)stream_); });
 }
 
 extern "C" int ideas_mbstd_bwd(void* gx, float* a_out, const void* gout, const void* x, int B, int C, int H, int W, int group, int feat,
@@ -262,8 +252,7 @@ extern "C" int ideas_mbstd_bwd(void* gx, float* a_out, const void* gout, const v
     if (rc) return rc;
     if (!gx || !a_out || !gout || !x) return IDEAS_E_NULL;
     a.eps = eps;
-    return dtype == IDEAS_BF16 ? mb_bwd<ideas_bf16>(gx, a_out, gout, x, a, (hipStream_t)stream_)
-                               : mb_bwd<float>(gx, a_out, gout, x, a, (hipStream_t)stream_);
+    return with_dtype(dtype, [&](auto c) { return mb_bwd<typename decltype(c)::type>(gx, a_out, gout, x, a, (hipStream_t)stream_); });
 }
 
 extern "C" int ideas_mbstd_bwd2(void* dgout, void* dx, void* workspace, const void* ggx, const void* x, const float* a_in, int B, int C,
@@ -273,6 +262,7 @@ extern "C" int ideas_mbstd_bwd2(void* dgout, void* dx, void* workspace, const vo
     if (rc) return rc;
     if (!dgout || !dx || !workspace || !ggx || !x || !a_in) return IDEAS_E_NULL;
     a.eps = eps;
-    return dtype == IDEAS_BF16 ? mb_bwd2<ideas_bf16>(dgout, dx, (double*)workspace, ggx, x, a_in, B, a, (hipStream_t)stream_)
-                               : mb_bwd2<float>(dgout, dx, (double*)workspace, ggx, x, a_in, B, a, (hipStream_t)stream_);
+    return with_dtype(dtype, [&](auto c) {
+        return mb_bwd2<typename decltype(c)::type>(dgout, dx, (double*)workspace, ggx, x, a_in, B, a, (hipStream_t)stream_);
+    });
 }

@@ -14,7 +14,7 @@
 // arithmetic is free: products and sums of the dot products are DOUBLE from the first multiply to the global accumulator
 // (ds_add_f64 / global_atomic_add_f64), and demod_bwd evaluates q = sum_i s^2 wsq, d = (q + eps)^-1/2 and both terms of gs in
 // double from the f32 styles and a double wsq; only gs / gq are rounded to f32, once.
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -125,7 +125,9 @@ __global__ __launch_bounds__(256) void demod_wgrad_kernel(float* __restrict__ gw
         for (int kx = 0; kx < KW; ++kx) gp[ky * gky + kx * gkx] = fmaf(acc, wp[ky * sky + kx * skx], gp[ky * gky + kx * gkx]);
 }
 
-template <typename T, typename V>      // T = element (float / bf16), V = four consecutive elements
+template <typename T> using vec4_of = std::conditional_t<std::is_same<T, float>::value, float4, ideas_bf16x4>;
+
+template <typename T, typename V>      // T = element (float / bf16), V = four consecutive elements (vec4_of<T>)
 __global__ __launch_bounds__(256) void pixel_dot_kernel(double* __restrict__ out, const T* __restrict__ a,
                                                         const T* __restrict__ g, int64_t P, int C,
                                                         int64_t pix_per_block) {
@@ -297,12 +299,11 @@ extern "C" int ideas_pixel_dot(double* out, const void* a, const void* g, int B,
     if (chunks < 1) chunks = 1;
     const int64_t per = ideas_cdiv(P, chunks);
     chunks = ideas_cdiv(P, per);
-    if (dtype == IDEAS_BF16)
-        hipLaunchKernelGGL((pixel_dot_kernel<ideas_bf16, ideas_bf16x4>), dim3((unsigned)chunks, (unsigned)B), dim3(256),
-                           (size_t)C * sizeof(double), (hipStream_t)stream, out, (const ideas_bf16*)a, (const ideas_bf16*)g, P, C, per);
-    else
-        hipLaunchKernelGGL((pixel_dot_kernel<float, float4>), dim3((unsigned)chunks, (unsigned)B), dim3(256),
-                           (size_t)C * sizeof(double), (hipStream_t)stream, out, (const float*)a, (const float*)g, P, C, per);
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((pixel_dot_kernel<T, vec4_of<T>>), dim3((unsigned)chunks, (unsigned)B), dim3(256), (size_t)C * sizeof(double),
+                           (hipStream_t)stream, out, (const T*)a, (const T*)g, P, C, per);
+    });
     return ideas_launch_status();
 }
 
@@ -322,13 +323,10 @@ extern "C" int ideas_act_bwd_dot(void* gpre, float* bias_grad, double* dot, cons
     if (chunks < 1) chunks = 1;
     const int64_t per = ideas_cdiv(P, chunks);
     chunks = ideas_cdiv(P, per);
-    if (dtype == IDEAS_BF16)
-        hipLaunchKernelGGL((act_bwd_dot_kernel<ideas_bf16, ideas_bf16x4>), dim3((unsigned)chunks, (unsigned)B), dim3(256),
-                           (size_t)2 * C * sizeof(double), (hipStream_t)stream, (ideas_bf16*)gpre, bias_grad, dot,
-                           (const ideas_bf16*)gy, (const ideas_bf16*)out, bias, gpre_scale, P, C, per, alpha, act_gain);
-    else
-        hipLaunchKernelGGL((act_bwd_dot_kernel<float, float4>), dim3((unsigned)chunks, (unsigned)B), dim3(256),
-                           (size_t)2 * C * sizeof(double), (hipStream_t)stream, (float*)gpre, bias_grad, dot, (const float*)gy,
-                           (const float*)out, bias, gpre_scale, P, C, per, alpha, act_gain);
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((act_bwd_dot_kernel<T, vec4_of<T>>), dim3((unsigned)chunks, (unsigned)B), dim3(256), (size_t)2 * C * sizeof(double),
+                           (hipStream_t)stream, (T*)gpre, bias_grad, dot, (const T*)gy, (const T*)out, bias, gpre_scale, P, C, per, alpha, act_gain);
+    });
     return ideas_launch_status();
 }

@@ -8,18 +8,18 @@
 // x / out / gy / gx are channels-innermost [B, P, C] in f32 or bf16, arithmetic is f32; noise, nw (ONE element in device memory,
 // never read on the host), bias and every gradient but gx are f32.  HBM-bound: 8 B/elem forward, 12 B/elem backward in f32.
 //
-// Work split.  A pixel is owned by a GROUP of G lanes, G = the power of two >= min(L, 64) where L = C / VW is the number of
-// 16-byte vectors (VW = 4 f32 / 8 bf16 elements; VW = 1 on the scalar path: any C, any alignment) of a pixel; lane l of the group
-// takes the vectors l, l + G, ...  G divides 64, so a group never straddles a wave, consecutive groups take consecutive pixels (a
+// Work split.  A pixel is owned by a GROUP of G = ideas_lane_group(L) lanes, where L = C / VW is the number of channel vectors of
+// a pixel (stream.hpp: VW = 4 f32 / 8 bf16 elements, or 1: any C, any alignment); lane l of the group takes the vectors
+// l, l + G, ...  G divides 64, so a group never straddles a wave, consecutive groups take consecutive pixels (a
 // wave reads contiguous memory), the noise value is loaded once per pixel and lane, and a lane stays on the same channels for the
 // whole kernel: the bias lives in registers and the bias gradient is summed in registers -> LDS -> one atomic per channel and
 // block, as ideas_fused_bias_act does.  The sum over the channels of a pixel (gnoise) is the xor butterfly inside the group.
 //
 // gnw is ONE address, so no floating-point atomics: a lane adds (sum of its gpre of a pixel) * noise in double, pixels in index
-// order; the wave combines with the xor butterfly, thread 0 adds the four waves in order and writes one double per block; a
+// order; block_sum_256 combines the block in a fixed order and thread 0 writes one double per block; a
 // one-wave kernel adds the <= IDEAS_NOISE_ACT_MAX_PARTIALS partials in a fixed order.  A [1,1,H,W] noise gradient is the sum over b,
 // in index order, of the per-sample rows.  out, gx, gnw and gnoise are bitwise reproducible; gbias (float atomics) is not.
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -32,50 +32,6 @@ struct NaArgs {
     int noise_per_sample; // 1: noise is [B, P], 0: [1, P]
     float slope, scale;
 };
-
-// VW consecutive elements <-> f32: one 16-byte access for (float, 4) and (bf16, 8), an element access for VW = 1
-template <typename T, int VW> struct na_io;
-template <typename T> struct na_io<T, 1> {
-    static __device__ __forceinline__ void load(const T* p, float (&f)[1]) { f[0] = ld1(p); }
-    static __device__ __forceinline__ void store(T* p, const float (&f)[1]) { st1(p, f[0]); }
-};
-template <> struct na_io<float, 4> {
-    static __device__ __forceinline__ void load(const float* p, float (&f)[4]) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&f)[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    }
-};
-template <> struct na_io<ideas_bf16, 8> {
-    static __device__ __forceinline__ void load(const ideas_bf16* p, float (&f)[8]) {
-        unpack8(*reinterpret_cast<const uint4*>(p), f, ideas_bf16{});
-    }
-    static __device__ __forceinline__ void store(ideas_bf16* p, const float (&f)[8]) {
-        *reinterpret_cast<uint4*>(p) = pack8(f, ideas_bf16{});
-    }
-};
-
-// VW consecutive f32 side values (bias): 16-byte loads on the vector paths (the host checked the alignment)
-template <int VW>
-__device__ __forceinline__ void na_load_f32(const float* p, float (&f)[VW]) {
-    if constexpr (VW == 1) {
-        f[0] = p[0];
-    } else {
-#pragma unroll
-        for (int q = 0; q < VW; q += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + q);
-            f[q] = v.x; f[q + 1] = v.y; f[q + 2] = v.z; f[q + 3] = v.w;
-        }
-    }
-}
-
-// the sum over the G lanes of a group (G a power of two <= 64), the same value in each of them; every lane of the wave calls it
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 template <typename T, int VW>
@@ -96,11 +52,11 @@ __global__ __launch_bounds__(256) void noise_act_fwd_kernel(T* __restrict__ out,
         }
         for (int v = l; v < a.L; v += a.G) {
             float bb[VW], xv[NA_U][VW];
-            na_load_f32<VW>(bias + v * VW, bb);
+            load_f32<VW>(bias + v * VW, bb);
 #pragma unroll
             for (int u = 0; u < NA_U; ++u) {
                 const int64_t pix = pix0 + u * ngrp;
-                if (pix < a.npix) na_io<T, VW>::load(x + pix * a.C + (int64_t)v * VW, xv[u]);
+                if (pix < a.npix) chan_io<T, VW>::load(x + pix * a.C + (int64_t)v * VW, xv[u]);
             }
 #pragma unroll
             for (int u = 0; u < NA_U; ++u) {
@@ -114,7 +70,7 @@ __global__ __launch_bounds__(256) void noise_act_fwd_kernel(T* __restrict__ out,
                     const float t = mul_then_add(nw, nz[u], xv[u][e]) + bb[e];
                     o[e] = mul_rn((t > 0.f) ? t : mul_rn(t, a.slope), a.scale);
                 }
-                na_io<T, VW>::store(out + pix * a.C + (int64_t)v * VW, o);
+                chan_io<T, VW>::store(out + pix * a.C + (int64_t)v * VW, o);
             }
         }
     }
@@ -160,8 +116,8 @@ __global__ __launch_bounds__(256) void noise_act_bwd_kernel(T* __restrict__ gx, 
             for (int u = 0; u < NA_U; ++u) {
                 const int64_t pix = pix0 + u * ngrp;
                 if (pix < a.npix) {
-                    na_io<T, VW>::load(gy + pix * a.C + (int64_t)v * VW, g[u]);
-                    na_io<T, VW>::load(out + pix * a.C + (int64_t)v * VW, o[u]);
+                    chan_io<T, VW>::load(gy + pix * a.C + (int64_t)v * VW, g[u]);
+                    chan_io<T, VW>::load(out + pix * a.C + (int64_t)v * VW, o[u]);
                 }
             }
 #pragma unroll
@@ -174,7 +130,7 @@ __global__ __launch_bounds__(256) void noise_act_bwd_kernel(T* __restrict__ gx, 
                     gp[e] = mul_rn((o[u][e] > 0.f) ? g[u][e] : mul_rn(g[u][e], a.slope), a.scale);
                     s += gp[e];
                 }
-                na_io<T, VW>::store(gx + pix * a.C + (int64_t)v * VW, gp);
+                chan_io<T, VW>::store(gx + pix * a.C + (int64_t)v * VW, gp);
                 csum[u] += s;
                 if (gbias) {
                     if (v == l) {
@@ -201,10 +157,8 @@ __global__ __launch_bounds__(256) void noise_act_bwd_kernel(T* __restrict__ gx, 
 #pragma unroll
         for (int e = 0; e < VW; ++e) atomicAdd(&s_bg[l * VW + e], accb[e]);
     }
-    accn = wave_sum(accn);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = accn;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+    accn = block_sum_256<double, true>(accn, s_part);
+    if (threadIdx.x == 0) part[blockIdx.x] = accn;
     if (gbias) {
         for (int c = threadIdx.x; c < a.C; c += 256) {
             const float v = s_bg[c];
@@ -239,16 +193,12 @@ int na_check(int B, int C, int H, int W, int noise_batch, int dtype, bool vec_al
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffLL) return IDEAS_E_SHAPE;
     if (noise_batch != 1 && noise_batch != B) return IDEAS_E_SHAPE;
     if (C > 8192) return IDEAS_E_SHAPE;                                       // the block's bias gradient lives in LDS
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    *vw = (vec_aligned && C % w == 0) ? w : 1;
-    const int L = C / *vw;
-    int G = 1;
-    while (G < L && G < 64) G <<= 1;
+    *vw = ideas_chan_vw(dtype, C, vec_aligned);
     a->P = (int64_t)H * W;
     a->npix = (int64_t)B * a->P;
     a->C = C;
-    a->L = L;
-    a->G = G;
+    a->L = C / *vw;
+    a->G = ideas_lane_group(a->L);
     a->noise_per_sample = noise_batch == B && B > 1;
     return IDEAS_OK;
 }
@@ -272,11 +222,10 @@ extern "C" int ideas_noise_bias_act(void* out, const void* x, const float* noise
     a.scale = scale;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid(na_grid(a, 4096));
-#define NA_FWD(T, VW)                                                                                                              \
-    hipLaunchKernelGGL((noise_act_fwd_kernel<T, VW>), grid, dim3(256), 0, stream, (T*)out, (const T*)x, noise, noise_weight, bias, a)
-    if (dtype == IDEAS_BF16) { if (vw == 8) NA_FWD(ideas_bf16, 8); else NA_FWD(ideas_bf16, 1); }
-    else { if (vw == 4) NA_FWD(float, 4); else NA_FWD(float, 1); }
-#undef NA_FWD
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((noise_act_fwd_kernel<T, c.VW>), grid, dim3(256), 0, stream, (T*)out, (const T*)x, noise, noise_weight, bias, a);
+    });
     return ideas_launch_status();
 }
 
@@ -297,18 +246,12 @@ extern "C" int ideas_noise_bias_act_bwd(void* gx, float* gbias, float* gnw, floa
     float* rows = fold ? reinterpret_cast<float*>(part + NA_MAX_BLOCKS) : gnoise;
     const dim3 grid(na_grid(a, NA_MAX_BLOCKS));
     const size_t lds = 4 * sizeof(double) + (size_t)C * sizeof(float);
-#define NA_BWD(T, VW)                                                                                                              \
-    do {                                                                                                                           \
-        if (gnoise)                                                                                                                \
-            hipLaunchKernelGGL((noise_act_bwd_kernel<T, VW, true>), grid, dim3(256), lds, stream, (T*)gx, gbias, part, rows,       \
-                               (const T*)gy, (const T*)out, noise, noise_weight, a);                                               \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((noise_act_bwd_kernel<T, VW, false>), grid, dim3(256), lds, stream, (T*)gx, gbias, part, rows,      \
-                               (const T*)gy, (const T*)out, noise, noise_weight, a);                                               \
-    } while (0)
-    if (dtype == IDEAS_BF16) { if (vw == 8) NA_BWD(ideas_bf16, 8); else NA_BWD(ideas_bf16, 1); }
-    else { if (vw == 4) NA_BWD(float, 4); else NA_BWD(float, 1); }
-#undef NA_BWD
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = gnoise ? noise_act_bwd_kernel<T, c.VW, true> : noise_act_bwd_kernel<T, c.VW, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, (T*)gx, gbias, part, rows, (const T*)gy, (const T*)out, noise,
+                           noise_weight, a);
+    });
     int st = ideas_launch_status();
     if (st) return st;
     hipLaunchKernelGGL(noise_act_fill_kernel, dim3(1), dim3(64), 0, stream, gnw, part, (int)grid.x);

@@ -5,7 +5,7 @@
 // 88 launches of ~59 us per iteration (5.2 ms) for 1.5 MB of output each.  Here: ONE launch per call, one thread per output
 // pixel (all channels), NHWC in and out; the boxes travel as a by-value kernel argument.  The gradient scatters with f32 atomics
 // into a zeroed image (crops overlap), as torch's own backward does.
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -103,10 +103,11 @@ extern "C" int ideas_patch_resize(void* y, const void* x, const int* boxes, int 
     const int64_t n = (int64_t)B * n_crop * out_h * out_w;
     const dim3 grid((unsigned)ideas_cdiv(n, 256)), block(256);
     hipStream_t s = (hipStream_t)stream_;
-#define GO(T, CC) hipLaunchKernelGGL((patch_resize_kernel<T, CC>), grid, block, 0, s, (T*)y, (const T*)x, bx, B, H, W, n_crop, out_h, out_w)
-    if (dtype == IDEAS_F32) { if (C == 3) GO(float, 3); else GO(float, 1); }
-    else { if (C == 3) GO(ideas_bf16, 3); else GO(ideas_bf16, 1); }
-#undef GO
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = C == 3 ? patch_resize_kernel<T, 3> : patch_resize_kernel<T, 1>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, (T*)y, (const T*)x, bx, B, H, W, n_crop, out_h, out_w);
+    });
     return ideas_launch_status();
 }
 
@@ -125,9 +126,10 @@ extern "C" int ideas_patch_resize_bwd(float* gx, const void* gy, const int* boxe
     }
     const int64_t n = (int64_t)B * n_crop * out_h * out_w;
     const dim3 grid((unsigned)ideas_cdiv(n, 256)), block(256);
-#define GO(T, CC) hipLaunchKernelGGL((patch_resize_bwd_kernel<T, CC>), grid, block, 0, s, gx, (const T*)gy, bx, B, H, W, n_crop, out_h, out_w)
-    if (dtype == IDEAS_F32) { if (C == 3) GO(float, 3); else GO(float, 1); }
-    else { if (C == 3) GO(ideas_bf16, 3); else GO(ideas_bf16, 1); }
-#undef GO
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = C == 3 ? patch_resize_bwd_kernel<T, 3> : patch_resize_bwd_kernel<T, 1>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, gx, (const T*)gy, bx, B, H, W, n_crop, out_h, out_w);
+    });
     return ideas_launch_status();
 }

@@ -6,9 +6,8 @@
 //   IDEAS_POOL_AVG_S1P1_VALID  F.avg_pool2d(x, 3, 1, 1, count_include_pad=False)   OH = H; divisor = the in-image taps (4 / 6 / 9)
 //   global average             adaptive_avg_pool2d(x, 1) -> float [B][C]
 //
-// Tensors are channels-innermost [B, H, W, C] in f32 or bf16, arithmetic is f32, one rounding at the store.  16-byte vectors along
-// C when C % VW == 0 (VW = 4 f32 / 8 bf16) and every pointer is 16-byte aligned, an element path (VW = 1) otherwise: the rule of
-// lpips.hip.
+// Tensors are channels-innermost [B, H, W, C] in f32 or bf16, arithmetic is f32, one rounding at the store; channel vectors of VW
+// elements by the rule of stream.hpp.
 //
 // Work split of the 3x3 windows: a thread owns one channel vector of a run of SEG consecutive outputs of one output row and walks
 // along it with the COLUMN reductions of the window in registers: col[ix] = the reduction of the (up to) three rows of input
@@ -21,35 +20,12 @@
 // (r0 + r1) + r2 down a column and then (c0 + c1) + c2 across the columns, missing taps contributing an exact +0, divided by the
 // count of in-image taps: a fixed order that does not depend on how the row is cut into runs, so the result is bitwise reproducible.
 // The global average adds the H W pixels of a channel in index order in one thread.  No atomics anywhere.
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
 constexpr int P3_SEG_S1 = 8;          // outputs per thread, stride 1: 30 column loads for 8 outputs
 constexpr int P3_SEG_S2 = 4;          // stride 2: 27 column loads for 4 outputs
-
-template <typename T, int VW> struct pl_io;
-template <typename T> struct pl_io<T, 1> {
-    static __device__ __forceinline__ void load(const T* p, float (&f)[1]) { f[0] = ld1(p); }
-    static __device__ __forceinline__ void store(T* p, const float (&f)[1]) { st1(p, f[0]); }
-};
-template <> struct pl_io<float, 4> {
-    static __device__ __forceinline__ void load(const float* p, float (&f)[4]) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&f)[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    }
-};
-template <> struct pl_io<ideas_bf16, 8> {
-    static __device__ __forceinline__ void load(const ideas_bf16* p, float (&f)[8]) {
-        unpack8(*reinterpret_cast<const uint4*>(p), f, ideas_bf16{});
-    }
-    static __device__ __forceinline__ void store(ideas_bf16* p, const float (&f)[8]) {
-        *reinterpret_cast<uint4*>(p) = pack8(f, ideas_bf16{});
-    }
-};
 
 struct Pool3Args {
     int B, H, W, C, OH, OW, L, NSEG;       // L = C / VW vectors per pixel, NSEG = runs per output row
@@ -67,7 +43,7 @@ __device__ __forceinline__ void pool3_column(const T* __restrict__ xb, const Poo
         const int iy = iy0 + r;
         if (iy < 0 || iy >= a.H) continue;
         float q[VW];
-        pl_io<T, VW>::load(xb + ((int64_t)iy * a.W + ix) * a.C + (int64_t)v * VW, q);
+        chan_io<T, VW>::load(xb + ((int64_t)iy * a.W + ix) * a.C + (int64_t)v * VW, q);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             if (AVG) col[e] = col[e] + q[e];
@@ -124,7 +100,7 @@ __global__ __launch_bounds__(256) void pool3x3_kernel(T* __restrict__ y, const T
                         o[e] = m;
                     }
                 }
-                pl_io<T, VW>::store(yrow + (int64_t)ow * a.C, o);
+                chan_io<T, VW>::store(yrow + (int64_t)ow * a.C, o);
 #pragma unroll
                 for (int e = 0; e < VW; ++e) { c0[e] = c1[e]; c1[e] = c2[e]; }
             }
@@ -141,7 +117,7 @@ __global__ __launch_bounds__(256) void pool3x3_kernel(T* __restrict__ y, const T
                     if (pool3_takes(c2[e], m)) m = c2[e];
                     o[e] = m;
                 }
-                pl_io<T, VW>::store(yrow + (int64_t)ow * a.C, o);
+                chan_io<T, VW>::store(yrow + (int64_t)ow * a.C, o);
 #pragma unroll
                 for (int e = 0; e < VW; ++e) c0[e] = c2[e];
             }
@@ -164,7 +140,7 @@ __global__ __launch_bounds__(256) void global_avg_kernel(float* __restrict__ out
         for (; q + 4 <= HW; q += 4) {
             float t[4][VW];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) pl_io<T, VW>::load(p + (int64_t)(q + k) * C, t[k]);
+            for (int k = 0; k < 4; ++k) chan_io<T, VW>::load(p + (int64_t)(q + k) * C, t[k]);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -172,7 +148,7 @@ __global__ __launch_bounds__(256) void global_avg_kernel(float* __restrict__ out
         }
         for (; q < HW; ++q) {
             float t[VW];
-            pl_io<T, VW>::load(p + (int64_t)q * C, t);
+            chan_io<T, VW>::load(p + (int64_t)q * C, t);
 #pragma unroll
             for (int e = 0; e < VW; ++e) s[e] = s[e] + t[e];
         }
@@ -205,8 +181,7 @@ extern "C" int ideas_pool3x3_fwd(void* y, const void* x, int B, int C, int H, in
     if ((int64_t)H * W * C >= 0x7fffffffLL) return IDEAS_E_SHAPE;
     if (!y || !x) return IDEAS_E_NULL;
     const int s2 = mode == IDEAS_POOL_MAX_S2;
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    const int vw = (ideas_aligned16(y) && ideas_aligned16(x) && C % w == 0) ? w : 1;
+    const int vw = ideas_chan_vw(dtype, C, ideas_aligned16(y) && ideas_aligned16(x));
     Pool3Args a;
     a.B = B; a.H = H; a.W = W; a.C = C;
     a.OH = s2 ? (H - 3) / 2 + 1 : H;
@@ -215,17 +190,13 @@ extern "C" int ideas_pool3x3_fwd(void* y, const void* x, int B, int C, int H, in
     a.NSEG = (int)ideas_cdiv(a.OW, s2 ? P3_SEG_S2 : P3_SEG_S1);
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid(pool3_grid((int64_t)B * a.OH * a.NSEG * a.L));
-#define POOL3(T, VW, S, AVG) hipLaunchKernelGGL((pool3x3_kernel<T, VW, S, AVG>), grid, dim3(256), 0, stream, (T*)y, (const T*)x, a)
-#define POOL3_MODE(T, VW)                                          \
-    do {                                                           \
-        if (mode == IDEAS_POOL_MAX_S2) POOL3(T, VW, 2, false);     \
-        else if (mode == IDEAS_POOL_MAX_S1P1) POOL3(T, VW, 1, false); \
-        else POOL3(T, VW, 1, true);                                \
-    } while (0)
-    if (dtype == IDEAS_BF16) { if (vw == 8) POOL3_MODE(ideas_bf16, 8); else POOL3_MODE(ideas_bf16, 1); }
-    else { if (vw == 4) POOL3_MODE(float, 4); else POOL3_MODE(float, 1); }
-#undef POOL3_MODE
-#undef POOL3
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto* kernel = mode == IDEAS_POOL_MAX_S2     ? pool3x3_kernel<T, c.VW, 2, false>
+                       : mode == IDEAS_POOL_MAX_S1P1 ? pool3x3_kernel<T, c.VW, 1, false>
+                                                     : pool3x3_kernel<T, c.VW, 1, true>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (T*)y, (const T*)x, a);
+    });
     return ideas_launch_status();
 }
 
@@ -234,14 +205,13 @@ extern "C" int ideas_global_avg_pool(float* out, const void* x, int B, int C, in
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return IDEAS_E_SHAPE;
     if ((int64_t)H * W >= 0x7fffffffLL / C) return IDEAS_E_SHAPE;
     if (!out || !x) return IDEAS_E_NULL;
-    const int w = dtype == IDEAS_BF16 ? 8 : 4;
-    const int vw = (ideas_aligned16(out) && ideas_aligned16(x) && C % w == 0) ? w : 1;
+    const int vw = ideas_chan_vw(dtype, C, ideas_aligned16(out) && ideas_aligned16(x));
     const int L = C / vw;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid(pool3_grid((int64_t)B * L));
-#define GAVG(T, VW) hipLaunchKernelGGL((global_avg_kernel<T, VW>), grid, dim3(256), 0, stream, out, (const T*)x, B, C, H * W, L)
-    if (dtype == IDEAS_BF16) { if (vw == 8) GAVG(ideas_bf16, 8); else GAVG(ideas_bf16, 1); }
-    else { if (vw == 4) GAVG(float, 4); else GAVG(float, 1); }
-#undef GAVG
+    with_chan(dtype, vw, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL((global_avg_kernel<T, c.VW>), grid, dim3(256), 0, stream, out, (const T*)x, B, C, H * W, L);
+    });
     return ideas_launch_status();
 }

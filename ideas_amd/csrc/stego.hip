@@ -8,7 +8,7 @@
 //
 // Every arithmetic step is one f32 operation in the reference's order (no contraction), so the results are bitwise those of the host
 // functions: see DESIGN.md "Steganography codec".
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -220,12 +220,11 @@ extern "C" int ideas_tensor_to_bits(void* bits, int* n_err, const void* z, const
     const float inv_step = (float)(1 << sigma) / 2.0f;
     const int64_t nbytes = ((int64_t)L * sigma + 7) / 8;
     hipStream_t stream = (hipStream_t)stream_;
-    if (dtype == IDEAS_F32)
-        hipLaunchKernelGGL(tensor_to_bits_kernel<float>, dim3((unsigned)B), dim3(256), 0, stream, (unsigned char*)bits, n_err,
-                           (const float*)z, (const unsigned char*)ref_bits, L, sigma, inv_step, nbytes);
-    else
-        hipLaunchKernelGGL(tensor_to_bits_kernel<ideas_bf16>, dim3((unsigned)B), dim3(256), 0, stream, (unsigned char*)bits, n_err,
-                           (const ideas_bf16*)z, (const unsigned char*)ref_bits, L, sigma, inv_step, nbytes);
+    with_dtype(dtype, [&](auto c) {
+        using T = typename decltype(c)::type;
+        hipLaunchKernelGGL(tensor_to_bits_kernel<T>, dim3((unsigned)B), dim3(256), 0, stream, (unsigned char*)bits, n_err, (const T*)z,
+                           (const unsigned char*)ref_bits, L, sigma, inv_step, nbytes);
+    });
     return ideas_launch_status();
 }
 
@@ -234,7 +233,6 @@ extern "C" int ideas_image_f32_to_u8(void* u8, float* y, const void* x, int B, i
     if (!u8 || !x) return IDEAS_E_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3)) return IDEAS_E_SHAPE;
     if (layout != IDEAS_NCHW && layout != IDEAS_NHWC) return IDEAS_E_UNSUPPORTED;
-    if (dtype == IDEAS_F32) return launch_image<float>(u8, y, x, B, C, H, W, layout, (hipStream_t)stream_);
-    if (dtype == IDEAS_BF16) return launch_image<ideas_bf16>(u8, y, x, B, C, H, W, layout, (hipStream_t)stream_);
-    return IDEAS_E_UNSUPPORTED;
+    if (dtype != IDEAS_F32 && dtype != IDEAS_BF16) return IDEAS_E_UNSUPPORTED;
+    return with_dtype(dtype, [&](auto c) { return launch_image<typename decltype(c)::type>(u8, y, x, B, C, H, W, layout, (hipStream_t)stream_); });
 }

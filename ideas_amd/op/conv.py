@@ -325,8 +325,6 @@ def conv_dgrad_raw(gy, w, g: ConvGeom, in_hw: Tuple[int, int], gain: float, lin=
         ph, pw = in_hw[0] + 2 * g.pad, in_hw[1] + 2 * g.pad
         gxp = conv_dgrad_raw(gy, w, gp, (ph, pw), gain, lin, lout)
         b, c = gxp.shape[0], gxp.shape[1]
-        if gxp.dtype == BF and c % 4:
-            return conv_dgrad_fold32(gxp, in_hw, g.pad)
         gx = torch.empty((b, c, in_hw[0], in_hw[1]), device=gxp.device, dtype=gxp.dtype, memory_format=CL)
         rc = _lib.load().ideas_reflect_fold(_lib.ptr(gx), _lib.ptr(gxp), b, in_hw[0], in_hw[1], c, g.pad, _lib.act_dtype(gxp),
                                             _lib.stream_ptr())
@@ -344,16 +342,6 @@ def conv_dgrad_raw(gy, w, g: ConvGeom, in_hw: Tuple[int, int], gain: float, lin=
         for L in launches:
             launch_fwd(gx, gy, L, gain, lin, lout)
     return gx
-
-
-def conv_dgrad_fold32(gxp: torch.Tensor, in_hw, pad: int) -> torch.Tensor:
-    """bf16 reflect fold for channel counts without a bf16 kernel (C % 4 != 0: the N-channel / RGB ends): f32 kernel on a cast."""
-    g32 = gxp.float()
-    b, c = g32.shape[0], g32.shape[1]
-    gx = torch.empty((b, c, in_hw[0], in_hw[1]), device=g32.device, dtype=torch.float32, memory_format=CL)
-    rc = _lib.load().ideas_reflect_fold(_lib.ptr(gx), _lib.ptr(g32), b, in_hw[0], in_hw[1], c, pad, _lib.F32, _lib.stream_ptr())
-    _lib.check(rc, "ideas_reflect_fold")
-    return gx.to(BF)
 
 
 _GU = {}

@@ -442,7 +442,9 @@ int ideas_noise_bias_act_bwd(void* gx, float* gbias, float* gnw, float* gnoise, 
                              float scale, int dtype, void* stream);
 
 /* Adjoint of ReflectionPad2d(pad) in NHWC: gx [B,H,W,C] = fold of gpadded [B,H+2pad,W+2pad,C] (mirrored border rows /
- * columns added back onto their sources).  Any C (16-byte vectors when C % 4 == 0).  Used by the input gradient of the reflect-padded 3x3 convs of
+ * columns added back onto their sources), IDEAS_F32 or IDEAS_BF16 (f32 sums, one rounding at the store).  Any C and any
+ * element-aligned pointers in both dtypes: 16-byte vectors when C % 4 == 0 (f32) / C % 8 == 0 (bf16) and both pointers are 16-byte
+ * aligned, element accesses otherwise; never IDEAS_E_ALIGN.  Used by the input gradient of the reflect-padded 3x3 convs of
  * E / Gstru / Ex (models.py:102-106). */
 int ideas_reflect_fold(void* gx, const void* gpadded, int B, int H, int W, int C, int pad, int dtype, void* stream);
 

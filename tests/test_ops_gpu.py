@@ -718,6 +718,78 @@ def test_reflect_fold_is_the_adjoint_of_reflection_pad(shape, pad):
     assert rel_err(out, ref) < 1e-6
 
 
+def _fold_raw(gx, gp, shape, pad, dtype):
+    """ideas_reflect_fold on raw NHWC buffers gx [B,H,W,C] / gp [B,H+2pad,W+2pad,C] (1-D views of any element alignment)"""
+    from ideas_amd import _lib
+    B, C, H, W = shape
+    rc = _lib.load().ideas_reflect_fold(_lib.ptr(gx), _lib.ptr(gp), B, H, W, C, pad, _lib.BF16 if dtype == torch.bfloat16 else _lib.F32,
+                                        _lib.stream_ptr())
+    assert rc == 0, rc
+
+
+def _fold_case(shape, pad):
+    """bf16-representable gradient of the padded tensor as NHWC f64, the f64 fold of it and of its magnitudes (autograd of F.pad)"""
+    B, C, H, W = shape
+    torch.manual_seed(sum(shape) + pad)
+    gp = torch.randn(B, C, H + 2 * pad, W + 2 * pad).bfloat16().double()
+    x = torch.zeros(B, C, H, W, dtype=torch.float64, requires_grad=True)
+    padded = F.pad(x, [pad] * 4, mode="reflect")
+    (ref,) = torch.autograd.grad(padded, x, gp, retain_graph=True)
+    (mag,) = torch.autograd.grad(padded, x, gp.abs())
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous()
+    return nhwc(gp), nhwc(ref), nhwc(mag)
+
+
+@pytest.mark.parametrize("C", [3, 6])
+def test_reflect_fold_bf16_takes_any_channel_count(C):
+    """bf16 fold with C % 4 != 0 (the RGB / N-channel ends, which used to be cast to f32, folded and cast back): bitwise the f32
+    kernel's result rounded once to bf16, and within rounding of autograd of F.pad(mode='reflect').  Bound: a sum of at most 9
+    terms in f32 (8 additions, each <= 2^-24 of the partial sum's magnitude <= mag) then one RNE rounding to bf16 (8 significand
+    bits: unit roundoff 2^-8): |got - ref| <= 2^-8 |ref| + 2^-20 mag."""
+    shape, pad = (2, C, 5, 4), 2
+    gp, ref, mag = _fold_case(shape, pad)
+    o32 = torch.empty(ref.shape, device="cuda")
+    _fold_raw(o32, gp.float().cuda(), shape, pad, torch.float32)
+    assert rel_err(o32, ref) < 1e-6
+    o = torch.empty(ref.shape, device="cuda", dtype=torch.bfloat16)
+    _fold_raw(o, gp.bfloat16().cuda(), shape, pad, torch.bfloat16)
+    assert torch.equal(o, o32.bfloat16())
+    assert bool(((o.double().cpu() - ref).abs() <= 2.0 ** -8 * ref.abs() + 2.0 ** -20 * mag).all())
+
+
+@pytest.mark.parametrize("dtype,off", [(torch.bfloat16, 4), (torch.float32, 1)], ids=["bf16_8_bytes", "f32_4_bytes"])
+def test_reflect_fold_on_views_off_a_16_byte_boundary_stays_inside_them(dtype, off):
+    """gx and gpadded as views that start 8 (bf16) / 4 (f32) bytes into their buffers: the values are the aligned call's, bit for
+    bit, and no byte of either buffer outside the views changes.  Each buffer is more than 8 times its view and pre-filled with a
+    sentinel, so a kernel that indexed 8-byte bf16 vectors by element (four times the tensor) would still land in memory this
+    test owns and show up as a changed guard band."""
+    shape, pad = (2, 8, 6, 9), 1
+    gp, ref, _ = _fold_case(shape, pad)
+    want = torch.empty(ref.shape, device="cuda")
+    _fold_raw(want, gp.float().cuda(), shape, pad, torch.float32)
+    assert rel_err(want, ref) < 1e-6
+    want = want.to(dtype)                                   # f32 sums in the same order, one rounding at the store
+
+    def guarded(n, fill):
+        buf = torch.full((8 * n + 64,), fill, device="cuda", dtype=dtype)
+        assert buf.data_ptr() % 16 == 0
+        return buf, buf[off:off + n]
+
+    gp_buf, gp_v = guarded(gp.numel(), -3.0)
+    gx_buf, gx_v = guarded(ref.numel(), 5.0)
+    gp_v.copy_(gp.reshape(-1))
+    assert gp_v.data_ptr() % 16 == off * gp_v.element_size() and gx_v.data_ptr() % 16 == off * gx_v.element_size()
+    gp_before, gx_before = gp_buf.clone(), gx_buf.clone()
+    _fold_raw(gx_v, gp_v, shape, pad, dtype)
+    torch.cuda.synchronize()
+    assert torch.equal(gx_v.view(want.shape), want)
+    as_bytes = lambda t: t.view(torch.uint8)
+    assert torch.equal(as_bytes(gp_buf), as_bytes(gp_before))
+    es, n = gx_v.element_size(), ref.numel()
+    assert torch.equal(as_bytes(gx_buf)[:off * es], as_bytes(gx_before)[:off * es])
+    assert torch.equal(as_bytes(gx_buf)[(off + n) * es:], as_bytes(gx_before)[(off + n) * es:])
+
+
 # --------------------------------------------------------------------------------------------- split-bf16 contraction
 def test_b3_weight_split_is_exact_and_step_major():
     """ideas_b3_split_weights: hi + mid + lo reproduces every f32 EXACTLY (incl. tiny / huge magnitudes), each plane is

@@ -132,6 +132,8 @@ _PROTOS = {
     "ideas_patch_resize": (C.c_int, [_P, _P, C.POINTER(C.c_int)] + [C.c_int] * 8 + [_P]),
     "ideas_patch_resize_bwd": (C.c_int, [_P, _P, C.POINTER(C.c_int)] + [C.c_int] * 9 + [_P]),
     "ideas_sizeof_prep_desc": (C.c_int, []),
+    "ideas_weight_prep_plan": (C.c_int, [C.POINTER(PrepDesc), C.c_int, C.POINTER(C.c_int64)]),
+    "ideas_weight_prep": (C.c_int, [C.POINTER(PrepDesc), C.c_int, _P, C.c_int, _P]),
     "ideas_weight_prep_batched": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ideas_sizeof_linear_seg": (C.c_int, []),
     "ideas_linear_fwd": (C.c_int, [C.POINTER(LinearSeg), C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -14,7 +14,7 @@
 //
 // The matrix pipe is then no longer the only limiter: a SIMD issues the split arithmetic through the same VALU port
 // as the MFMAs, so the kernel is built to keep everything else OFF the vector ALU:
-//   * weights are split once per launch by ideas_b3_split_weights into step-major planes [3][K/16][Cout][16] bf16
+//   * weights are split once per optimiser step (weight_prep.hip, IDEAS_PREP_B3_SPLIT) into step-major planes [3][K/16][Cout][16] bf16
 //     (K-steps ordered (ci/16, ty, tx): taps innermost, so a pixel neighbourhood is revisited in consecutive steps):
 //     the B tile of a K-step is one contiguous 4 KB block, copied global -> LDS without any arithmetic;
 //   * activations are fetched with raw buffer loads: 32-bit offsets, and padding taps get an out-of-range offset,
@@ -38,71 +38,6 @@
 #include "conv_launch.hpp"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------
-// weights: f32 [Cout][K] (K = (ty,tx,ci) contiguous)  ->  bf16 planes [3][K/16][Cout][16], K-step = (ci/16, ty, tx)
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void split_weights_kernel(uint2* __restrict__ dst, const float4* __restrict__ w, int Cout, int K,
-                                                            int Cin) {
-    const int64_t n4 = (int64_t)Cout * (K / 4);
-    const int64_t plane = (int64_t)Cout * K / 4;   // uint2 (4 bf16) units per plane
-    const int ntaps = K / Cin;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        const int k = (int)(i % (K / 4)) * 4;      // k = tap * Cin + ci in the f32 matrix
-        const int n = (int)(i / (K / 4));
-        const int tap = k / Cin, ci = k - tap * Cin;
-        const int step = (ci >> 4) * ntaps + tap;  // K-steps run over the taps of one 16-channel chunk, then the next chunk
-        const Split4 s = split4(w[i]);
-        const int64_t o = ((int64_t)step * Cout + n) * 4 + ((ci & 15) >> 2);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[pl * plane + o] = s.p[pl];
-    }
-}
-
-// The same planes read straight from the parameter: element (n, ty, tx, ci) of the launch's matrix at
-// w[n*sn + ty*sty + tx*stx + ci*sc] (see ideas_bf16_pack_weights_strided, conv_bf16.hip).
-template <bool UNIT>
-__device__ __forceinline__ void split_weights_strided_body(uint2* __restrict__ dst, const float* __restrict__ w, int Cout, int TY, int TX,
-                                                           int Cin, int64_t sn, int64_t sty, int64_t stx, int64_t sc, int64_t bid,
-                                                           int64_t nblk) {
-    const int c4 = Cin / 4, ntaps = TY * TX;
-    const int64_t n4 = (int64_t)Cout * ntaps * c4;
-    const int64_t plane = n4;
-    for (int64_t i = bid * 256 + threadIdx.x; i < n4; i += nblk * 256) {
-        int n, tap, ci;
-        if (UNIT) {
-            ci = (int)(i % c4) * 4;
-            tap = (int)((i / c4) % ntaps);
-            n = (int)(i / ((int64_t)c4 * ntaps));
-        } else {
-            n = (int)(i % Cout);
-            ci = (int)((i / Cout) % c4) * 4;
-            tap = (int)(i / ((int64_t)Cout * c4));
-        }
-        const int ty = tap / TX, tx = tap - ty * TX;
-        const float* src = w + n * sn + ty * sty + tx * stx + ci * sc;
-        const float4 v = UNIT ? *reinterpret_cast<const float4*>(src) : make_float4(src[0], src[sc], src[2 * sc], src[3 * sc]);
-        const int step = (ci >> 4) * ntaps + tap;
-        const Split4 s = split4(v);
-        const int64_t o = ((int64_t)step * Cout + n) * 4 + ((ci & 15) >> 2);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[pl * plane + o] = s.p[pl];
-    }
-}
-
-template <bool UNIT>
-__global__ __launch_bounds__(256) void split_weights_strided_kernel(uint2* __restrict__ dst, const float* __restrict__ w, int Cout,
-                                                                    int TY, int TX, int Cin, int64_t sn, int64_t sty, int64_t stx,
-                                                                    int64_t sc) {
-    split_weights_strided_body<UNIT>(dst, w, Cout, TY, TX, Cin, sn, sty, stx, sc, blockIdx.x, gridDim.x);
-}
-
-__global__ __launch_bounds__(256) void split_weights_batched_kernel(const ideas_prep_desc* __restrict__ tbl, int n) {
-    int local, nblk;
-    const ideas_prep_desc* d = prep_lookup(tbl, n, local, nblk);
-    if (d->unit) split_weights_strided_body<true>((uint2*)d->dst, d->w, d->a[0], d->a[1], d->a[2], d->a[3], d->s[0], d->s[1], d->s[2], d->s[3], local, nblk);
-    else split_weights_strided_body<false>((uint2*)d->dst, d->w, d->a[0], d->a[1], d->a[2], d->a[3], d->s[0], d->s[1], d->s[2], d->s[3], local, nblk);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // forward family
@@ -418,7 +353,7 @@ extern "C" int ideas_b3_conv_supported(const ideas_conv_params* p) {
 }
 
 // called by ideas_conv_igemm for dtype IDEAS_F32_B3 once the arguments are validated; `wplanes` comes from
-// ideas_b3_split_weights
+// ideas_b3_split_weights (weight_prep.hip)
 #ifndef SMALL_GRID_TILES
 #define SMALL_GRID_TILES 160
 #endif
@@ -452,36 +387,4 @@ int ideas_b3_fwd_multi(int n, void* y, const void* x, const void* const* wplanes
     if (cout > 64) return launch_b3_multi_cfg<2, 2, 2, 2>(n, y, x, wplanes, in_scale, out_scale, ps, stream);
     if (cout > 32) return launch_b3_multi_cfg<2, 2, 2, 1>(n, y, x, wplanes, in_scale, out_scale, ps, stream);
     return launch_b3_multi_cfg<4, 1, 1, 1>(n, y, x, wplanes, in_scale, out_scale, ps, stream);
-}
-
-void ideas_b3_split_batched(const ideas_prep_desc* tbl, int n, int blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(split_weights_batched_kernel, dim3(blocks), dim3(256), 0, stream, tbl, n);
-}
-
-extern "C" int ideas_b3_split_weights(void* planes, const void* wmat, int Cout, int K, int Cin, void* stream_) {
-    if (!planes || !wmat) return IDEAS_E_NULL;
-    if (Cout <= 0 || K <= 0 || Cin <= 0 || K % Cin) return IDEAS_E_SHAPE;
-    if (Cin % 16 || !ideas_aligned16(planes) || !ideas_aligned16(wmat)) return IDEAS_E_ALIGN;
-    const int64_t n4 = (int64_t)Cout * (K / 4);
-    const int blocks = ideas_prep_blocks(n4);
-    hipLaunchKernelGGL(split_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes,
-                       (const float4*)wmat, Cout, K, Cin);
-    return ideas_launch_status();
-}
-
-extern "C" int ideas_b3_split_weights_strided(void* planes, const float* w, int Cout, int TY, int TX, int Cin, int64_t sn, int64_t sty,
-                                              int64_t stx, int64_t sc, void* stream_) {
-    if (!planes || !w) return IDEAS_E_NULL;
-    if (Cout <= 0 || TY <= 0 || TX <= 0 || Cin <= 0) return IDEAS_E_SHAPE;
-    if (Cin % 16 || !ideas_aligned16(planes)) return IDEAS_E_ALIGN;
-    const int64_t n4 = (int64_t)Cout * TY * TX * (Cin / 4);
-    const int blocks = ideas_prep_blocks(n4);
-    const bool unit = sc == 1 && ideas_aligned16(w) && sn % 4 == 0 && sty % 4 == 0 && stx % 4 == 0;
-    if (unit)
-        hipLaunchKernelGGL(split_weights_strided_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes, w, Cout,
-                           TY, TX, Cin, sn, sty, stx, sc);
-    else
-        hipLaunchKernelGGL(split_weights_strided_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes, w, Cout,
-                           TY, TX, Cin, sn, sty, stx, sc);
-    return ideas_launch_status();
 }

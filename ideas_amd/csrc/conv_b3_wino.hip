@@ -13,7 +13,7 @@
 // fetches and 24 MFMAs per wave and step.  K-steps run over (16-channel chunk, ky) with ky innermost.
 //   A: thread (row r, quad kq) fetches the four window columns d0..d3 (buffer loads, padding -> out-of-range offset ->
 //      hardware zeros), forms V0..V3 in f32, splits the 16 values and writes 12 eight-byte groups;
-//   B: the transformed weights arrive pre-split from ideas_b3_wino_split_weights as [4 v][3 planes][step][Cout][16] bf16,
+//   B: the transformed weights arrive pre-split from weight_prep.hip (IDEAS_PREP_B3_WINO) as [4 v][3 planes][step][Cout][16] bf16,
 //      which IS the MFMA operand layout (row = channel, 16 K values contiguous): every wave fetches its six operand
 //      registers for the next step straight from global memory (one coalesced 1 KB buffer load each) -- the weights never
 //      pass through LDS, which halves the LDS write traffic and the operand ds_reads of the first version.
@@ -45,63 +45,6 @@ constexpr int XROW = 36;          // floats per row of the exchange buffer (32 +
 // condition admits on its own.
 constexpr int WINO_N256_MIN_TILES = 129;
 constexpr int WINO_N256_ANY_TILES = 2048;
-
-// ---------------------------------------------------------------------------------------------------------------
-// weights: element (n, ky, kx, c) at w[base + n*sn + ky*sky + kx*skx + c*sc]  ->  U planes [4][3][3*C/16][N][16] bf16
-//   forward : n = o, c = i on the OHWI parameter          (sn = 9I, sky = 3I, skx = I, sc = 1, base = 0)
-//   dgrad   : n = i, c = o, taps flipped, same parameter  (sn = 1, sky = -3I, skx = -I, sc = 9I, base = 8I)
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wino_split_weights_body(uint2* __restrict__ dst, const float* __restrict__ w, int N, int C, int64_t sn,
-                                                        int64_t sky, int64_t skx, int64_t sc, int64_t base, int64_t bid, int64_t nblk) {
-    const int64_t total = (int64_t)N * 3 * (C / 4);
-    const int nsteps = 3 * (C / 16);
-    const int64_t plane = (int64_t)nsteps * N * 4;        // uint2 units per (v, plane)
-    for (int64_t i = bid * 256 + threadIdx.x; i < total; i += nblk * 256) {
-        const int c = (int)(i % (C / 4)) * 4;
-        const int ky = (int)((i / (C / 4)) % 3);
-        const int n = (int)(i / (3 * (C / 4)));
-        float wk[3][4];
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) wk[kx][e] = w[base + n * sn + ky * sky + kx * skx + (c + e) * sc];
-        // The transformed weights are the same for every pixel of every sample, so an error in them is a COHERENT error of the
-        // outputs: it does not average out in the backward's sums over 65 536 pixels (weight gradient, style / demodulation dot
-        // products) the way per-pixel rounding does.  Rounding U twice in f32 ((w0 + w2) + w1, 1.2e-7 relative) made G's late-layer
-        // gradients sit 4x further from f64 than stock f32 arithmetic (tests/test_nets_gpu.py::test_full_width_gradients_vs_oracle);
-        // the sums are exact in double, and the three planes are cut from the double: hi + mid + lo = U to ~2^-26.
-        double u[4][4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double s = (double)wk[0][e] + (double)wk[2][e];
-            u[0][e] = wk[0][e];
-            u[1][e] = (s + (double)wk[1][e]) * 0.5;
-            u[2][e] = (s - (double)wk[1][e]) * 0.5;
-            u[3][e] = wk[2][e];
-        }
-        const int step = (c >> 4) * 3 + ky;
-        const int64_t o = ((int64_t)step * N + n) * 4 + ((c & 15) >> 2);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            Split4 s;
-            split2d(u[v][0], u[v][1], s.p[0].x, s.p[1].x, s.p[2].x);
-            split2d(u[v][2], u[v][3], s.p[0].y, s.p[1].y, s.p[2].y);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) dst[(v * 3 + pl) * plane + o] = s.p[pl];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void wino_split_weights_kernel(uint2* __restrict__ dst, const float* __restrict__ w, int N, int C,
-                                                                 int64_t sn, int64_t sky, int64_t skx, int64_t sc, int64_t base) {
-    wino_split_weights_body(dst, w, N, C, sn, sky, skx, sc, base, blockIdx.x, gridDim.x);
-}
-
-__global__ __launch_bounds__(256) void wino_split_weights_batched_kernel(const ideas_prep_desc* __restrict__ tbl, int n) {
-    int local, nblk;
-    const ideas_prep_desc* d = prep_lookup(tbl, n, local, nblk);
-    wino_split_weights_body((uint2*)d->dst, d->w, d->a[0], d->a[1], d->s[0], d->s[1], d->s[2], d->s[3], d->s[4], local, nblk);
-}
 
 // NH = 1: 256 threads, tile 64 pairs x  64 channels, K-step 16 channels (4 waves  = the 4 Winograd components)
 // NH = 2: 512 threads, tile 64 pairs x 128 channels, K-step 32 channels (8 waves  = 4 components x 2 channel halves):
@@ -844,22 +787,6 @@ extern "C" int ideas_b3_wino_supported(const ideas_conv_params* p) {
            p->OH == p->IH && p->OW == p->IW && p->YH == p->IH && p->YW == p->IW && p->osy == 1 && p->osx == 1 && p->ooy == 0 &&
            p->oox == 0 && (p->IW & 1) == 0 && p->Cin % 16 == 0 && (!p->reflect || (p->IH >= 2 && p->IW >= 2)) &&
            (int64_t)p->B * p->IH * p->IW * p->Cin * 4 < 0xffffffffLL && (int64_t)p->Cin * p->Cout * 72 < 0xffffffffLL;
-}
-
-void ideas_b3_wino_split_batched(const ideas_prep_desc* tbl, int n, int blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(wino_split_weights_batched_kernel, dim3(blocks), dim3(256), 0, stream, tbl, n);
-}
-
-extern "C" int ideas_b3_wino_split_weights(void* planes, const void* w, int N, int C, int64_t sn, int64_t sky, int64_t skx,
-                                           int64_t sc, int64_t base, void* stream_) {
-    if (!planes || !w) return IDEAS_E_NULL;
-    if (N <= 0 || C <= 0) return IDEAS_E_SHAPE;
-    if (C % 16 || !ideas_aligned16(planes)) return IDEAS_E_ALIGN;
-    const int64_t total = (int64_t)N * 3 * (C / 4);
-    const int blocks = ideas_prep_blocks(total);
-    hipLaunchKernelGGL(wino_split_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (uint2*)planes,
-                       (const float*)w, N, C, sn, sky, skx, sc, base);
-    return ideas_launch_status();
 }
 
 // The ONE place that chooses among the Winograd kernels of a forward: ideas_b3_wino_fwd launches what this says, and the

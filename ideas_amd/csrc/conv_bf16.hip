@@ -9,9 +9,9 @@
 //     * activations go global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds): no staging registers, no ds_write.  The DMA
 //       writes lane l's 16 bytes at base + 16 l, so the swizzle and the im2col gather both live in the per-lane SOURCE
 //       offset; a padding tap gets offset 0xffffffff, for which the DMA writes zeros (probed: tools/probes/dma.hip);
-//     * weights are packed once per optimiser step (ideas_bf16_pack_weights) into [K/32][Cout][32] bf16 with that swizzle
+//     * weights are packed once per optimiser step (weight_prep.hip, IDEAS_PREP_BF16_PACK) into [K/32][Cout][32] bf16 with that swizzle
 //       already applied, so a B tile is one contiguous block that the DMA copies linearly;
-//     * modulated convs (per-sample input scale s[b, ci]): the pack kernel writes one bf16 pack per sample, w * s[b, :] -- the
+//     * modulated convs (per-sample input scale s[b, ci]): the pack kernel (weight_prep.hip) writes one bf16 pack per sample, w * s[b, :] -- the
 //       reference's per-sample weights (stylegan2/model.py:240-248), but bf16, swizzled and alive for one launch only (at most
 //       151 MB for a 512x512x3x3 layer at B = 32, 0.06 ms of HBM time next to a 0.9 ms convolution); M tiles are cut per image
 //       (the last tile of an image is partial) and a block DMAs the B tiles of ITS image, so both operand paths stay pure DMA;
@@ -45,95 +45,6 @@ constexpr int ROW = 64;         // bytes per LDS row of the forward kernel
 
 __device__ __forceinline__ uint4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// weights: f32 [Cout][K] (K = (ty, tx, ci) contiguous) -> bf16 [K/32][Cout][32], K-step = (ci/32, ty, tx), 16-byte chunk c of
-// row n stored at position c ^ ((n >> 2) & 3).  With `scale` (float [B][Cin]): B packs, pack b holds w[n][k] * scale[b][ci(k)]
-// -- the reference's per-sample modulated weights (stylegan2/model.py:240-248), as bf16 and only for the life of one launch.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pack_weights_kernel(uint4* __restrict__ dst, const float4* __restrict__ w,
-                                                           const float* __restrict__ scale, int Cout, int K, int Cin) {
-    const int64_t n8 = (int64_t)Cout * (K / 8);
-    const int ntaps = K / Cin;
-    const int b = blockIdx.y;
-    const float* sb = scale ? scale + (int64_t)b * Cin : nullptr;
-    uint4* out = dst + (int64_t)b * n8;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-        const int k = (int)(i % (K / 8)) * 8;
-        const int n = (int)(i / (K / 8));
-        const int tap = k / Cin, ci = k - tap * Cin;
-        const int step = (ci >> 5) * ntaps + tap;
-        const int c = (ci & 31) >> 3;
-        float4 u = w[2 * i], v = w[2 * i + 1];
-        if (sb) {
-            const float4 s0 = *reinterpret_cast<const float4*>(sb + ci), s1 = *reinterpret_cast<const float4*>(sb + ci + 4);
-            u = make_float4(u.x * s0.x, u.y * s0.y, u.z * s0.z, u.w * s0.w);
-            v = make_float4(v.x * s1.x, v.y * s1.y, v.z * s1.z, v.w * s1.w);
-        }
-        out[((int64_t)step * Cout + n) * 4 + (c ^ ((n >> 2) & 3))] =
-            make_uint4(ideas_pk_bf16(u.x, u.y), ideas_pk_bf16(u.z, u.w), ideas_pk_bf16(v.x, v.y), ideas_pk_bf16(v.z, v.w));
-    }
-}
-
-// The same pack read straight from the PARAMETER: element (n, ty, tx, ci) of the launch's weight matrix lies at
-// w[n*sn + ty*sty + tx*stx + ci*sc] (f32 elements) -- the forward matrix of an [O,I,KH,KW] tensor of any strides, the
-// phase-sliced transposed matrix of an input gradient, or the matrix of a transposed conv -- so no permuted / sliced f32 copy is
-// materialised first (one launch instead of copy + pack, and 2-4 launches fewer per conv and step than torch's slicing).
-template <bool UNIT>
-__device__ __forceinline__ void pack_weights_strided_body(uint4* __restrict__ dst, const float* __restrict__ w,
-                                                          const float* __restrict__ scale, int Cout, int TY, int TX, int Cin, int64_t sn,
-                                                          int64_t sty, int64_t stx, int64_t sc, int b, int64_t bid, int64_t nblk) {
-    const int c8 = Cin / 8, ntaps = TY * TX;
-    const int64_t n8 = (int64_t)Cout * ntaps * c8;
-    const float* sb = scale ? scale + (int64_t)b * Cin : nullptr;
-    uint4* out = dst + (int64_t)b * n8;
-    for (int64_t i = bid * 256 + threadIdx.x; i < n8; i += nblk * 256) {
-        // UNIT (sc == 1): consecutive threads read consecutive 32-byte pieces of one (n, tap) row; otherwise consecutive
-        // threads take consecutive n (the contiguous index of a transposed read) of one (tap, 8-channel chunk)
-        int n, tap, ci;
-        if (UNIT) {
-            ci = (int)(i % c8) * 8;
-            tap = (int)((i / c8) % ntaps);
-            n = (int)(i / ((int64_t)c8 * ntaps));
-        } else {
-            n = (int)(i % Cout);
-            ci = (int)((i / Cout) % c8) * 8;
-            tap = (int)(i / ((int64_t)Cout * c8));
-        }
-        const int ty = tap / TX, tx = tap - ty * TX;
-        const float* src = w + n * sn + ty * sty + tx * stx + ci * sc;
-        float v[8];
-        if (UNIT) {
-            const float4 u0 = *reinterpret_cast<const float4*>(src), u1 = *reinterpret_cast<const float4*>(src + 4);
-            v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = src[j * sc];
-        }
-        if (sb) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] *= sb[ci + j];
-        }
-        const int step = (ci >> 5) * ntaps + tap;
-        const int c = (ci & 31) >> 3;
-        out[((int64_t)step * Cout + n) * 4 + (c ^ ((n >> 2) & 3))] =
-            make_uint4(ideas_pk_bf16(v[0], v[1]), ideas_pk_bf16(v[2], v[3]), ideas_pk_bf16(v[4], v[5]), ideas_pk_bf16(v[6], v[7]));
-    }
-}
-
-template <bool UNIT>
-__global__ __launch_bounds__(256) void pack_weights_strided_kernel(uint4* __restrict__ dst, const float* __restrict__ w,
-                                                                   const float* __restrict__ scale, int Cout, int TY, int TX, int Cin,
-                                                                   int64_t sn, int64_t sty, int64_t stx, int64_t sc) {
-    pack_weights_strided_body<UNIT>(dst, w, scale, Cout, TY, TX, Cin, sn, sty, stx, sc, blockIdx.y, blockIdx.x, gridDim.x);
-}
-
-__global__ __launch_bounds__(256) void pack_weights_batched_kernel(const ideas_prep_desc* __restrict__ tbl, int n) {
-    int local, nblk;
-    const ideas_prep_desc* d = prep_lookup(tbl, n, local, nblk);
-    if (d->unit) pack_weights_strided_body<true>((uint4*)d->dst, d->w, nullptr, d->a[0], d->a[1], d->a[2], d->a[3], d->s[0], d->s[1], d->s[2], d->s[3], 0, local, nblk);
-    else pack_weights_strided_body<false>((uint4*)d->dst, d->w, nullptr, d->a[0], d->a[1], d->a[2], d->a[3], d->s[0], d->s[1], d->s[2], d->s[3], 0, local, nblk);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -908,42 +819,6 @@ extern "C" int ideas_bf16_wgrad_supported(const ideas_conv_params* p, int scaled
         return 0;
     (void)scaled;
     return 1;
-}
-
-extern "C" int ideas_bf16_pack_weights(void* pack, const void* wmat, const float* in_scale, int B, int Cout, int K, int Cin,
-                                       void* stream_) {
-    if (!pack || !wmat) return IDEAS_E_NULL;
-    if (Cout <= 0 || K <= 0 || Cin <= 0 || K % Cin || B <= 0 || B > 65535) return IDEAS_E_SHAPE;
-    if (Cin % 32 || !ideas_aligned16(pack) || !ideas_aligned16(wmat) || (in_scale && !ideas_aligned16(in_scale))) return IDEAS_E_ALIGN;
-    if (!in_scale && B != 1) return IDEAS_E_SHAPE;
-    const int64_t n8 = (int64_t)Cout * (K / 8);
-    const int blocks = ideas_prep_blocks(n8);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks, in_scale ? B : 1), dim3(256), 0, (hipStream_t)stream_, (uint4*)pack,
-                       (const float4*)wmat, in_scale, Cout, K, Cin);
-    return ideas_launch_status();
-}
-
-void ideas_bf16_pack_batched(const ideas_prep_desc* tbl, int n, int blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(pack_weights_batched_kernel, dim3(blocks), dim3(256), 0, stream, tbl, n);
-}
-
-extern "C" int ideas_bf16_pack_weights_strided(void* pack, const float* w, const float* in_scale, int B, int Cout, int TY, int TX,
-                                               int Cin, int64_t sn, int64_t sty, int64_t stx, int64_t sc, void* stream_) {
-    if (!pack || !w) return IDEAS_E_NULL;
-    if (Cout <= 0 || TY <= 0 || TX <= 0 || Cin <= 0 || B <= 0 || B > 65535) return IDEAS_E_SHAPE;
-    if (Cin % 32 || !ideas_aligned16(pack) || (in_scale && !ideas_aligned16(in_scale))) return IDEAS_E_ALIGN;
-    if (!in_scale && B != 1) return IDEAS_E_SHAPE;
-    const int64_t n8 = (int64_t)Cout * TY * TX * (Cin / 8);
-    const int blocks = ideas_prep_blocks(n8);
-    const bool unit = sc == 1 && ideas_aligned16(w) && sn % 4 == 0 && sty % 4 == 0 && stx % 4 == 0;
-    const dim3 grid(blocks, in_scale ? B : 1);
-    if (unit)
-        hipLaunchKernelGGL(pack_weights_strided_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream_, (uint4*)pack, w, in_scale, Cout,
-                           TY, TX, Cin, sn, sty, stx, sc);
-    else
-        hipLaunchKernelGGL(pack_weights_strided_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream_, (uint4*)pack, w, in_scale, Cout,
-                           TY, TX, Cin, sn, sty, stx, sc);
-    return ideas_launch_status();
 }
 
 // the forward tiles <WM, WN, MT, NT> of ideas_bf16_fwd and ideas_bf16_fwd_multi

@@ -19,8 +19,6 @@ static inline unsigned ideas_nhwc_bytes(int B, int H, int W, int C, int elt) { r
 static inline unsigned ideas_x_bytes(const ideas_conv_params* p, int elt) { return ideas_nhwc_bytes(p->B, p->IH, p->IW, p->Cin, elt); }
 static inline unsigned ideas_gy_bytes(const ideas_conv_params* p, int elt) { return ideas_nhwc_bytes(p->B, p->YH, p->YW, p->Cout, elt); }
 static inline bool ideas_grid_fits(int64_t blocks) { return blocks <= 0x7fffffffLL; }      // a 1-D grid
-// grid of the weight-preparation kernels (grid-stride over n vectors)
-static inline int ideas_prep_blocks(int64_t n) { return (int)(n / 256 + 1 < 2048 ? n / 256 + 1 : 2048); }
 
 // ---- device query: what include/ideas_hip.h allows to be memoised per process, initialised once and thread-safely ---------------
 inline int ideas_cu_count() {                                  // (inline, not static: ONE value for the whole library)

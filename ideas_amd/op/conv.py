@@ -59,7 +59,7 @@ BLUR_CONV_MOD_MIN_BLOCKS = int(_os.environ.get("IDEAS_BLUR_CONV_MOD_MIN_BLOCKS",
 def wino_weights(w_ohwi: torch.Tensor) -> torch.Tensor:
     """[O,3,3,I] (o, ky, kx, ci) -> U [4,O,3,I]: U0 = w0, U1 = (w0+w1+w2)/2, U2 = (w0-w1+w2)/2, U3 = w2 over kx."""
     # (sums in double, ONE rounding to f32: the transformed weights are shared by every pixel, so their rounding error is
-    #  coherent across the backward's pixel reductions -- see csrc/conv_b3_wino.hip::wino_split_weights_kernel)
+    #  coherent across the backward's pixel reductions -- see csrc/weight_prep.hip::prep_wino)
     w_ohwi = w_ohwi.double()
     w0, w1, w2 = w_ohwi[:, :, 0], w_ohwi[:, :, 1], w_ohwi[:, :, 2]
     s = w0 + w2
@@ -77,36 +77,15 @@ def _b3_wino_ok(g: "ConvGeom", cin: int, cout: int, width: int) -> bool:
             and cin % 16 == 0 and cout % 4 == 0)
 
 
-def _prep(op: int, planes: int, taps: int, dims, strides, src: int, vec: int, aligned: bool = True):
-    """The ``prep`` tuple of ``conv_plan.cached`` for a derived-weight form of ``planes`` bf16 planes over ``taps`` x prod(``dims``)
-    elements, read ``vec`` channels (the last of ``dims``) at a time through ``strides`` from address ``src``: the same call as one
-    entry of the batched refill.  None where the batched kernels' channel granularity (4 * vec) does not divide the channels.
-    ``aligned``: the form has a 16-byte fast path, taken for unit channel stride and 16-byte aligned rows."""
-    if dims[-1] % (4 * vec):
-        return None
-    n = taps
-    for d in dims:
-        n *= d
-    unit = aligned and strides[3] == 1 and src % 16 == 0 and strides[0] % 4 == 0 and strides[1] % 4 == 0 and strides[2] % 4 == 0
-    return (op, planes * n, tuple(dims), tuple(strides), unit, src, n // vec)
-
-
 def b3_wino_planes(w: torch.Tensor, transposed: bool) -> torch.Tensor:
     """Winograd-transformed, split weights of a [O,I,3,3] parameter for ideas_conv3x3_wino(IDEAS_F32_B3): the forward matrix,
     or (transposed) the flipped one of the input gradient, read straight from the OHWI memory of the parameter."""
     o, i = w.shape[0], w.shape[1]
     n, c, *st = (i, o, 1, -3 * i, -i, 9 * i, 8 * i) if transposed else (o, i, 9 * i, 3 * i, i, 1, 0)
-    wm0 = w.permute(0, 2, 3, 1)
-
-    def make():
-        wm = wm0 if wm0.is_contiguous() else wm0.contiguous()
-        pl = torch.empty(12 * n * 3 * c, device=w.device, dtype=BF)
-        _lib.check(_lib.load().ideas_b3_wino_split_weights(_lib.ptr(pl), _lib.ptr(wm), n, c, *st, _lib.stream_ptr()),
-                   "ideas_b3_wino_split_weights")
-        return pl
-    # read in place: the same call as an entry of the batched refill
-    prep = _prep(_lib.PREP_B3_WINO, 12, 3, (n, c), st, wm0.data_ptr(), 4, aligned=False) if wm0.is_contiguous() and i % 16 == 0 else None
-    return conv_plan.cached(w, ("b3wino", transposed), make, prep)
+    wm, key = w.permute(0, 2, 3, 1), ("b3wino", transposed)
+    if not wm.is_contiguous():            # from an OHWI copy, made on a miss only, which the batched refill cannot name
+        return conv_plan.cached(w, key, lambda: conv_plan.derived_weight(_lib.PREP_B3_WINO, None, None, (n, c), st, wm.contiguous()))
+    return conv_plan.derived_weight(_lib.PREP_B3_WINO, w, key, (n, c), st, wm, batchable=i % 16 == 0)
 
 
 def launch_wino(y, x, umat, b, cin, h, w, cout, gain, reflect, in_scale=None, out_scale=None, bias=None, resid=None,
@@ -134,38 +113,15 @@ def bf16_pack(L: Launch, in_scale=None) -> torch.Tensor:
     sample, w * in_scale[b]; memoised on (weights, styles) for the iteration -- G is applied to the same texture code two or three
     times -- inside a byte budget (conv_plan.STYLE_BUDGET_MB, oldest entries dropped first: the packs of a style that cannot
     recur, e.g. the D phase's T2, do not stay resident until the G step)."""
-    v = L.wview
-    nb = 1 if in_scale is None else L.B
-
-    def make():
-        pk = torch.empty(nb * L.Cout * L.TY * L.TX * L.Cin, device=v.device, dtype=BF)
-        sn, sty, stx, sc = v.stride()
-        _lib.check(_lib.load().ideas_bf16_pack_weights_strided(_lib.ptr(pk), _lib.ptr(v), _lib.ptr(in_scale), nb, L.Cout, L.TY, L.TX,
-                                                                L.Cin, sn, sty, stx, sc, _lib.stream_ptr()),
-                   "ideas_bf16_pack_weights_strided")
-        return pk
-    if L.wsrc is None:
-        return make()
-    if in_scale is not None:           # per-sample packs: the same (weights, styles) pair comes back within an iteration (conv_plan.cached_on)
-        return conv_plan.cached_on(L.wsrc, ("bf16s",) + L.wkey, in_scale, make, budget=True)
-    prep = _prep(_lib.PREP_BF16_PACK, 1, 1, (L.Cout, L.TY, L.TX, L.Cin), v.stride(), v.data_ptr(), 8)
-    return conv_plan.cached(L.wsrc, ("bf16",) + L.wkey, make, prep)
+    key = None if L.wsrc is None else ("bf16s" if in_scale is not None else "bf16",) + L.wkey
+    return conv_plan.derived_weight(_lib.PREP_BF16_PACK, L.wsrc, key, (L.Cout, L.TY, L.TX, L.Cin), L.wview.stride(), L.wview,
+                                    in_scale, 1 if in_scale is None else L.B)
 
 
 def b3_planes(L: Launch) -> torch.Tensor:
     """Split-bf16 planes of a forward-family weight matrix for ideas_conv_igemm(IDEAS_F32_B3), memoised per optimiser step."""
-    v = L.wview
-
-    def split():
-        pl = torch.empty(3 * L.Cout * L.TY * L.TX * L.Cin, device=v.device, dtype=BF)
-        sn, sty, stx, sc = v.stride()
-        _lib.check(_lib.load().ideas_b3_split_weights_strided(_lib.ptr(pl), _lib.ptr(v), L.Cout, L.TY, L.TX, L.Cin, sn, sty, stx, sc,
-                                                               _lib.stream_ptr()), "ideas_b3_split_weights_strided")
-        return pl
-    if L.wsrc is None:
-        return split()
-    prep = _prep(_lib.PREP_B3_SPLIT, 3, 1, (L.Cout, L.TY, L.TX, L.Cin), v.stride(), v.data_ptr(), 4)
-    return conv_plan.cached(L.wsrc, ("b3",) + L.wkey, split, prep)
+    return conv_plan.derived_weight(_lib.PREP_B3_SPLIT, L.wsrc, None if L.wsrc is None else ("b3",) + L.wkey,
+                                    (L.Cout, L.TY, L.TX, L.Cin), L.wview.stride(), L.wview)
 
 
 def _params(L: Launch, gain: float, accumulate: bool = False, act: bool = False, alpha: float = 0.2,

@@ -104,8 +104,8 @@ class Launch:
 _CACHE = None
 
 # Batched refill.  Most derived forms are "parameter -> bf16 planes / pack" by one of three kernels; remade one by one they are ~390
-# launches of 5-25 us per iteration (f32; ~290 in bf16), most too small to fill the chip.  A miss that comes with a ``prep``
-# description (op, destination elements, dims, strides, source address) is remembered across iterations; from then on
+# launches of 5-25 us per iteration (f32; ~290 in bf16), most too small to fill the chip.  A miss made by ``derived_weight`` is
+# remembered across iterations as (op, its planned ideas_prep_desc, destination elements); from then on
 # ``cache_begin`` (all of them) and ``cache_clear(params)`` (those derived from the stepped parameters) remake the remembered forms
 # with ONE launch per op (ideas_weight_prep_batched) into persistent buffers, and the first use finds them in the cache.
 # Entries whose parameter died or moved are dropped.  IDEAS_PREFILL=0 keeps the one-by-one path.
@@ -121,12 +121,40 @@ _OUT_BUF = {}       # cache key -> its persistent destination buffer, shared by 
 _DEPS = {}          # cache key -> addresses of further parameters the entry was derived from (cached_on(..., deps=...))
 
 
-def _prep_state(keys):
+def derived_weight(op: int, w, key, dims, strides, src: torch.Tensor, in_scale=None, nb: int = 1, batchable: bool = True):
+    """A derived-weight form ``op`` (_lib.PREP_*, csrc/weight_prep.hip) of the matrix with ``dims`` read through ``strides`` (f32
+    elements) from the first element of ``src``: planned by the library (ideas_weight_prep_plan: an error code = this form does not
+    take the shape, raised), allocated, made by one launch (ideas_weight_prep).  Memoised per optimiser step on the parameter (view)
+    ``w`` under ``key`` (None: no caching) and recorded for the batched refill with the descriptor the launch used -- unless
+    ``batchable`` is off (``src`` is a temporary).  ``in_scale`` [nb, Cin]: per-sample bf16 packs, memoised on (weights, styles) inside
+    the byte budget instead."""
     import ctypes as C
+    from .. import _lib
+    rec = []
+
+    def make():
+        lib = _lib.load()
+        d, numel = _lib.PrepDesc(), C.c_int64()
+        d.w, d.s[:len(strides)], d.a[:len(dims)] = src.data_ptr(), strides, dims      # (a third of the constructor's time)
+        _lib.check(lib.ideas_weight_prep_plan(C.byref(d), op, C.byref(numel)), "ideas_weight_prep_plan")
+        out = torch.empty(nb * numel.value, device=src.device, dtype=torch.bfloat16)
+        d.dst = out.data_ptr()
+        _lib.check(lib.ideas_weight_prep(C.byref(d), op, _lib.ptr(in_scale), nb, _lib.stream_ptr()), "ideas_weight_prep")
+        rec.append((op, d, numel.value))
+        return out
+    if w is None:
+        return make()
+    if in_scale is not None:           # the same (weights, styles) pair comes back within an iteration
+        return cached_on(w, key, in_scale, make, budget=True)
+    return cached(w, key, make, (lambda: rec[0]) if batchable else None)
+
+
+def _prep_state(keys):
     from .. import _lib
     st = _PREP_STATE.get(keys)
     if st is not None:
         return st
+    import ctypes as C
     by_op = {}
     for k in keys:
         by_op.setdefault(_RECORDED[k][0][0], []).append(k)
@@ -136,21 +164,15 @@ def _prep_state(keys):
         outs, block0 = [], 0
         dev = None
         for i, k in enumerate(ks):
-            (_, numel, a, sv, unit, src, work), ref, _p0 = _RECORDED[k]
+            (_, desc, numel), ref, _p0 = _RECORDED[k]
             base = ref()
             dev = base.device
             out = _OUT_BUF.get(k)
             if out is None or out.numel() != numel or out.device != dev:
                 out = _OUT_BUF[k] = torch.empty(numel, device=dev, dtype=torch.bfloat16)
-            nb = int(min(work // 256 + 1, 2048))
-            d = descs[i]
-            d.dst, d.w = out.data_ptr(), src
-            for j in range(5):
-                d.s[j] = sv[j] if j < len(sv) else 0
-            for j in range(4):
-                d.a[j] = a[j] if j < len(a) else 0
-            d.unit, d.block0, d.nblocks = int(unit), block0, nb
-            block0 += nb
+            C.memmove(C.byref(descs[i]), C.byref(desc), C.sizeof(desc))      # as planned: unit and nblocks are the library's
+            descs[i].dst, descs[i].block0 = out.data_ptr(), block0
+            block0 += desc.nblocks
             outs.append((k, out))
         table = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
         st.append((op, table, len(ks), block0, outs))
@@ -255,8 +277,8 @@ def cache_end() -> None:
 
 def cached(w: torch.Tensor, key, make, prep=None):
     """`make()` memoised on (storage address, shape, key) while the cache is on and `w` is (a view of) a Parameter.
-    ``prep`` = (op, destination bf16 elements, dims a[<=4], strides s[<=5], unit, source address, work items): the same result as
-    one entry of a batched launch (see _prefill); remembered on a miss."""
+    ``prep``: called after a miss, returns (op, the planned ideas_prep_desc of the launch ``make`` ran, destination bf16 elements) --
+    the same result as one entry of a batched launch (see _prefill); remembered."""
     if _CACHE is None:
         return make()
     base = w._base if w._base is not None else w
@@ -268,7 +290,7 @@ def cached(w: torch.Tensor, key, make, prep=None):
         v = make()
         _CACHE[k] = v
         if prep is not None and PREFILL and k not in _RECORDED:
-            _RECORDED[k] = (prep, _weakref.ref(base), base.data_ptr())
+            _RECORDED[k] = (prep(), _weakref.ref(base), base.data_ptr())
             _PREP_STATE.clear()
             _KEYS_OF.clear()
     return v

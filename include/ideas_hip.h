@@ -45,7 +45,11 @@ extern "C" {
                                     ideas_image_u8_to_f32, ideas_stream_create, ideas_linear_fwd / _bwd_x / _bwd_w +
                                     ideas_sizeof_linear_seg (minimum version for the EqualLinear API).  The Python binding
                                     (ideas_amd/_lib.py) requires `ideas_abi_version() == 4` EXACTLY, before it looks any symbol
-                                    up: a library of another version, older or newer, is refused. */
+                                    up: a library of another version, older or newer, is refused.  Version 4 also REMOVED
+                                    ideas_b3_wino_wgrad_supported and the IDEAS_F32_B3 form of ideas_conv3x3_wino_wgrad.
+                                    Entry points marked "additive within ABI 4" below came later without a bump: the binding
+                                    looks every one of them up, so a version-4 library built before one of them fails there
+                                    with the missing symbol's name. */
 
 enum { IDEAS_NCHW = 0, IDEAS_NHWC = 1 };
 /* `dtype` of the convolution entry points.  Tensors are f32 in HBM for both values.
@@ -188,7 +192,7 @@ typedef struct ideas_conv_params {
 int ideas_conv_igemm(void* y, const void* x, const void* wmat, const float* in_scale, const float* out_scale,
                      const float* bias, const void* resid, const ideas_conv_params* p, int dtype, void* stream);
 
-/* Split-bf16 ("b3") operand preparation for dtype IDEAS_F32_B3 (csrc/conv_b3.hip).
+/* Split-bf16 ("b3") operand preparation for dtype IDEAS_F32_B3 (kernels: csrc/conv_b3.hip; preparation: csrc/weight_prep.hip).
  *   ideas_b3_conv_supported  1 if ideas_conv_igemm(..., IDEAS_F32_B3, ...) covers the geometry (Cin % 16 == 0, <= 32 taps,
  *                            x and the weight planes < 4 GiB: the kernel addresses them with 32-bit buffer offsets).
  *   ideas_b3_split_weights   wmat f32 [Cout][K] (the same matrix ideas_conv_igemm takes for IDEAS_F32) -> `planes`,
@@ -216,7 +220,7 @@ int ideas_b3_wino_supported(const ideas_conv_params* p);
 int ideas_b3_wino_split_weights(void* planes, const void* w, int N, int C, int64_t sn, int64_t sky, int64_t skx, int64_t sc,
                                 int64_t base, void* stream);
 
-/* bf16 mixed precision (dtype IDEAS_BF16 of ideas_conv_igemm / ideas_conv_wgrad; csrc/conv_bf16.hip).
+/* bf16 mixed precision (dtype IDEAS_BF16 of ideas_conv_igemm / ideas_conv_wgrad; csrc/conv_bf16.hip, the pack: csrc/weight_prep.hip).
  *   ideas_bf16_conv_supported   1 if ideas_conv_igemm(..., IDEAS_BF16, ...) covers the geometry: Cin % 32 == 0, Cout % 4 == 0,
  *                               <= 32 taps, tensors < 4 GiB (`scaled`: an in_scale will be passed; M tiles are then cut per sample
  *                               and the block scales its weight tile by in_scale[b, :]).
@@ -235,26 +239,39 @@ int ideas_bf16_pack_weights(void* pack, const void* wmat, const float* in_scale,
 /* ideas_bf16_pack_weights reading the matrix through strides (see ideas_b3_split_weights_strided). */
 int ideas_bf16_pack_weights_strided(void* pack, const float* w, const float* in_scale, int B, int Cout, int TY, int TX, int Cin,
                                     int64_t sn, int64_t sty, int64_t stx, int64_t sc, void* stream);
-/* The three derived-weight forms above for MANY parameters in one launch per form (the forms are remade after every optimiser
- * step: one batched launch instead of ~100 small ones per form and network group).  `table` = n descriptors IN DEVICE MEMORY
- * (the caller builds them once: parameter and destination addresses do not change between steps), `op` selects the form, and
- * block0 / nblocks give each descriptor's share of the `total_blocks` 256-thread blocks (descriptors sorted by block0, first 0,
- * contiguous).  Per element the kernels run the single-tensor bodies: results are bitwise those of the calls they replace.
+/* The three derived-weight forms above as ONE kind of job (csrc/weight_prep.hip): an ideas_prep_desc names the destination, the first
+ * element of the matrix, its dims and its strides in floats.  The entry points above fill one and take the same path.
  *   IDEAS_PREP_B3_SPLIT   dst = planes of ideas_b3_split_weights_strided(w, Cout=a[0], TY=a[1], TX=a[2], Cin=a[3], s = sn,sty,stx,sc)
  *   IDEAS_PREP_B3_WINO    dst = planes of ideas_b3_wino_split_weights(w, N=a[0], C=a[1], s = sn,sky,skx,sc,base)
- *   IDEAS_PREP_BF16_PACK  dst = pack of ideas_bf16_pack_weights_strided(w, NULL, 1, Cout=a[0], TY=a[1], TX=a[2], Cin=a[3], s = ...) */
+ *   IDEAS_PREP_BF16_PACK  dst = pack of ideas_bf16_pack_weights_strided(w, in_scale, B, Cout=a[0], TY=a[1], TX=a[2], Cin=a[3], s = ...)
+ * ideas_weight_prep_plan  host arithmetic only, no device call: checks a[] for form `op` (IDEAS_E_SHAPE: a dimension <= 0;
+ *                         IDEAS_E_ALIGN: channels a[3] % 16 (split), a[3] % 32 (pack), a[1] % 16 (Winograd)), FILLS d->unit (the
+ *                         16-byte read path: s[3] == 1, w 16-byte aligned, s[0..2] multiples of 4; never for the Winograd form) and
+ *                         d->nblocks (256-thread blocks of the job) and reports the bf16 elements of the destination (of ONE pack).
+ *                         dst and block0 are not read.  This is the only statement of those rules: callers do not restate them.
+ * ideas_weight_prep       one job from a HOST descriptor (planned here again: unit / nblocks of the argument are not trusted).
+ *                         in_scale / B belong to the pack: float [B][a[3]], 16-byte aligned, B <= 65535 packs of dst_elems each;
+ *                         without a scale B must be 1, and the other forms take in_scale == NULL (IDEAS_E_UNSUPPORTED).
+ * ideas_weight_prep_batched  MANY planned jobs of one form in one launch (the forms are remade after every optimiser step: one
+ *                         launch instead of ~100 small ones per form and network group).  `table` = n descriptors IN DEVICE MEMORY
+ *                         (the caller builds them once: parameter and destination addresses do not change between steps), each as
+ *                         ideas_weight_prep_plan left it plus dst and block0: block0 / nblocks give each descriptor's share of the
+ *                         `total_blocks` blocks (descriptors sorted by block0, first 0, contiguous).  No scale.
+ * Per element every route runs the same body: results are bitwise the same.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
 enum { IDEAS_PREP_B3_SPLIT = 0, IDEAS_PREP_B3_WINO = 1, IDEAS_PREP_BF16_PACK = 2 };
 typedef struct ideas_prep_desc {
     void* dst;
     const float* w;
     int64_t s[5];
     int a[4];
-    int unit;        /* 1: unit channel stride and 16-byte aligned rows (vector reads), as the single-tensor entry points decide */
+    int unit;        /* 1: unit channel stride and 16-byte aligned rows (vector reads); set by ideas_weight_prep_plan */
     int block0;
-    int nblocks;
+    int nblocks;     /* set by ideas_weight_prep_plan */
     int pad_;
 } ideas_prep_desc;
 int ideas_sizeof_prep_desc(void);
+int ideas_weight_prep_plan(ideas_prep_desc* d, int op, int64_t* dst_elems);
+int ideas_weight_prep(const ideas_prep_desc* host_desc, int op, const float* in_scale, int B, void* stream);
 int ideas_weight_prep_batched(const ideas_prep_desc* table, int n, int op, int total_blocks, void* stream);
 /* 1 if ideas_conv_direct / ideas_conv_wgrad_direct with IDEAS_BF16 are the intended path for the geometry: the HBM-bound
  * pointwise layers with <= 8 input or output channels (from-RGB, to-RGB and their gradients).  Everything else without a bf16

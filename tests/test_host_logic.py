@@ -116,6 +116,62 @@ def test_splitk_plans_match_pinned():
         assert hashlib.sha256(rows.tobytes()).digest() == bytes(g[name + "/sha256"]), name
 
 
+def prep_plan_reference(op, a, s, w_addr):
+    """What the commit before csrc/weight_prep.hip computed for a derived-weight job, transcribed from its three places: the entry
+    points' validation (ideas_b3_split_weights_strided, ideas_b3_wino_split_weights, ideas_bf16_pack_weights_strided), op/conv.py's
+    ``_prep`` (the `unit` flag and the work-item count the batched kernels trusted) and the grid rule, written as ideas_prep_blocks in C
+    and again in op/conv_plan.py.  Returns (code, unit, nblocks, dst_elems); a = dims, s = strides in floats, w_addr = source address."""
+    from ideas_amd import _lib
+    wino = op == _lib.PREP_B3_WINO
+    vec, planes, taps = {_lib.PREP_B3_SPLIT: (4, 3, 1), _lib.PREP_B3_WINO: (4, 12, 3), _lib.PREP_BF16_PACK: (8, 1, 1)}[op]
+    dims = a[:2] if wino else a[:4]
+    if any(d <= 0 for d in dims):
+        return (-2, None, None, None)                        # IDEAS_E_SHAPE
+    if dims[-1] % (4 * vec):
+        return (-4, None, None, None)                        # IDEAS_E_ALIGN: Cin % 16 (b3), Cin % 32 (bf16), C % 16 (wino)
+    n = taps
+    for d in dims:
+        n *= d
+    unit = (not wino) and s[3] == 1 and w_addr % 16 == 0 and s[0] % 4 == 0 and s[1] % 4 == 0 and s[2] % 4 == 0
+    work = n // vec
+    return (0, int(unit), min(work // 256 + 1, 2048), planes * n)
+
+
+def test_weight_prep_plan_is_the_rule_it_replaced():
+    """ideas_weight_prep_plan (csrc/weight_prep.hip: the one statement of the channel granularities, the element counts, the 16-byte
+    `unit` rule and the grid rule of the derived-weight kernels) against prep_plan_reference over dims around every granularity and
+    block-count boundary, strides with each of sc / sn / sty / stx on and off the rule, and sources at 0 / 4 / 8 / 12 mod 16."""
+    import itertools
+    from ideas_amd import _lib
+    lib = _lib.load()
+    strides = [(1152, 384, 128, 1), (1152, 384, 128, 2), (1153, 384, 128, 1), (1154, 384, 128, 1), (1152, 385, 128, 1),
+               (1152, 386, 128, 1), (1152, 384, 129, 1), (1152, 384, 130, 1), (1, -384, -128, 1152), (0, 0, 0, 1), (-4, 8, -12, 1),
+               (1156, 388, 132, 9)]
+    couts = (-1, 0, 1, 3, 5, 15, 16, 17, 255, 256, 257, 8191, 8192, 32736, 32752, 32768)
+    cins = (-16, 0, 1, 15, 16, 17, 31, 32, 33, 48, 64, 96, 128)
+    taps = ((1, 1), (1, 3), (3, 3), (0, 3), (3, -1))
+    n, numel, seen = 0, ctypes.c_int64(), set()
+    for op in (_lib.PREP_B3_SPLIT, _lib.PREP_B3_WINO, _lib.PREP_BF16_PACK):
+        for (co, ci, (ty, tx)), st, addr in itertools.product(itertools.product(couts, cins, taps), strides, (0, 4, 8, 12)):
+            # the Winograd form has a = (N, C) and five strides (the last one the base offset); it reads no other field
+            a = (co, ci, 7 * ty, 0) if op == _lib.PREP_B3_WINO else (co, ty, tx, ci)
+            if op == _lib.PREP_B3_WINO and tx != 3:
+                continue
+            d = _lib.PrepDesc(dst=0, w=(1 << 20) + addr, s=st + (addr,), a=a, unit=7, block0=5, nblocks=-3)
+            numel.value = -1
+            rc = lib.ideas_weight_prep_plan(ctypes.byref(d), op, ctypes.byref(numel))
+            want = prep_plan_reference(op, a, st, (1 << 20) + addr)
+            got = (rc, d.unit, d.nblocks, numel.value) if rc == 0 else (rc, None, None, None)
+            assert got == want, (op, a, st, addr, got, want)
+            assert d.block0 == 5 and d.dst is None and list(d.a) == list(a)         # the plan fills unit and nblocks, nothing else
+            seen.add(want[:3])
+            n += 1
+    assert n > 5000
+    assert {(-2, None, None), (-4, None, None), (0, 0, 1), (0, 1, 1), (0, 1, 2048), (0, 0, 2048), (0, 1, 2047)} <= seen
+    assert lib.ideas_weight_prep_plan(ctypes.byref(d), 3, ctypes.byref(numel)) == -3                 # unknown form
+    assert lib.ideas_weight_prep_plan(None, 0, ctypes.byref(numel)) == -1 and lib.ideas_weight_prep_plan(ctypes.byref(d), 0, None) == -1
+
+
 def test_ops_fail_loudly_on_cpu_tensors():
     import ideas_amd.op as op
     with pytest.raises(RuntimeError, match="no CPU fallback"):

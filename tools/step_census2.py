@@ -18,7 +18,7 @@ from ideas_amd.optim import fuse_optimizers  # noqa: E402
 
 FIELDS = [f for f, _ in _lib.ConvParams._fields_]
 SKIP = {"ideas_abi_version", "ideas_sizeof_conv_params", "ideas_strerror", "ideas_sizeof_prep_desc", "ideas_sizeof_linear_seg",
-        "ideas_stream_create", "ideas_stream_destroy", "ideas_linear_bwd_x_workspace"}
+        "ideas_stream_create", "ideas_stream_destroy", "ideas_linear_bwd_x_workspace", "ideas_weight_prep_plan"}
 
 
 def conv_sig(p):

@@ -80,6 +80,7 @@ NOISE_ACT_MAX_PARTIALS = 2048     # include/ideas_hip.h::IDEAS_NOISE_ACT_MAX_PAR
 LPIPS_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_LPIPS_MAX_PARTIALS
 POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1_VALID = 0, 1, 2     # include/ideas_hip.h::IDEAS_POOL_*
 FEATURE_STATS_MAX_DIM = 4096     # include/ideas_hip.h::IDEAS_FEATURE_STATS_MAX_DIM
+PATH_LERP, PATH_SLERP, PATH_MAX_DIM = 0, 1, 4096     # include/ideas_hip.h::IDEAS_PATH_*
 
 _P = C.c_void_p
 _PROTOS = {
@@ -159,6 +160,8 @@ _PROTOS = {
     "ideas_bits_to_tensor": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "ideas_tensor_to_bits": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ideas_image_f32_to_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),
+    "ideas_path_endpoints": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P]),
+    "ideas_pair_prepare": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)] + [C.c_int] * 7 + [_P]),
 }
 EXPORTS = tuple(_PROTOS)
 ABI_VERSION = 4          # include/ideas_hip.h::IDEAS_ABI_VERSION

@@ -139,6 +139,21 @@ class PerceptualLoss(nn.Module):
         with torch.no_grad():
             return self.net(self.scaling_layer(x))
 
+    def pair_distance(self, prepared: torch.Tensor) -> torch.Tensor:
+        """``prepared``: [2B, 3, h, w], the output of ``op.pair_prepare`` -- already through the scaling layer, the first sides of the
+        B pairs in the first half-batch and the second sides in the other.  ONE backbone pass over all 2B samples, each tap's head on
+        its two halves -> [B] float32.  No gradient."""
+        if prepared.dim() != 4 or prepared.shape[0] % 2 or prepared.shape[0] == 0:
+            raise RuntimeError(f"pair_distance expects the [2B, 3, h, w] output of op.pair_prepare, got {tuple(prepared.shape)}")
+        b = prepared.shape[0] // 2
+        with torch.no_grad():
+            taps = self.net(prepared)
+            val = None
+            for k, tap in enumerate(taps):
+                r = self.head(tap[:b], tap[b:], self.lin(k))
+                val = r if val is None else val + r
+        return val.float()
+
     def forward(self, pred: torch.Tensor, target: torch.Tensor, normalize: bool = False, ret_per_layer: bool = False):
         """``pred``, ``target``: [N, 3, H, W] in [-1, 1] ([0, 1] with ``normalize=True``) -> [N, 1, 1, 1] float32."""
         if normalize:

@@ -600,6 +600,36 @@ int ideas_tensor_to_bits(void* bits, int* n_err, const void* z, const void* ref_
 int ideas_image_f32_to_u8(void* u8, float* y, const void* x, int B, int C, int H, int W, int layout, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Perceptual path length (stylegan2/ppl.py): the small steps around the generator and the VGG, csrc/ppl.hip and csrc/patchify.hip.
+ * B counts PATHS: both tensors of either call hold 2B rows / samples.
+ *   ideas_path_endpoints   lat, out float [2B][D] row-major, t float [B].  Rows 2i and 2i + 1 of lat are the ends a, b of path i;
+ *                              out[2i] = f(a, b, t[i]),   out[2i + 1] = f(a, b, t[i] + eps)         (the sum formed in f32)
+ *                          -- the torch.stack([e0, e1], 1).view(2B, D) order of ppl.py:76.  mode:
+ *       IDEAS_PATH_LERP    f = a + (b - a) * t, one rounding per operation in that order (no contraction): bitwise the torch expression
+ *       IDEAS_PATH_SLERP   a, b normalised (x / sqrt(sum x^2)); d = a . b; p = t acos(d); c = normalize(b - d a);
+ *                          f = normalize(a cos p + c sin p) (ppl.py:16-24).  d is NOT clamped, as in the reference: identical or
+ *                          opposite ends (c = 0 / 0) and an all-zero end give a row of NaN there and here.
+ *                          One wave per path, both rows from one read of a and b, the row sums as cross-lane butterflies in a fixed
+ *                          order (bitwise reproducible, no atomics).  1 <= D <= IDEAS_PATH_MAX_DIM (IDEAS_E_UNSUPPORTED above: a
+ *                          path's two rows stay in registers).  16-byte accesses when D % 4 == 0 and lat, out are 16-byte aligned.
+ *   ideas_pair_prepare     x [2B][H][W][3], y [2B][out_h][out_w][3], channels-innermost, f32 or bf16 (f32 arithmetic, one rounding
+ *                          at the store).  The crop `box` (host int[4] = y, x, h, w in source pixels, inside the image) of every
+ *                          sample is resized bilinearly to out_h x out_w (F.interpolate(mode="bilinear", align_corners=False), the
+ *                          arithmetic of ideas_patch_resize), then per channel (v - shift[c]) / scale[c] with a true division
+ *                          (LPIPS's ScalingLayer; shift, scale: host float[3], copied into the kernel's arguments).  Sample 2i of x
+ *                          lands at y[i], sample 2i + 1 at y[B + i]: the two sides of every pair become two contiguous half-batches.
+ *                          A box of the output's size has the taps (1, 0): y is (x - shift) / scale bit for bit.  Forward only.
+ * IDEAS_E_NULL: a NULL pointer.  IDEAS_E_SHAPE: B, D, H, W, out_h or out_w <= 0, a box that leaves the image or has a non-positive
+ * size.  IDEAS_E_UNSUPPORTED: D above the cap, an unknown mode, C != 3, a dtype other than f32 / bf16.  Every check comes before any
+ * launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#define IDEAS_PATH_LERP 0
+#define IDEAS_PATH_SLERP 1
+#define IDEAS_PATH_MAX_DIM 4096
+int ideas_path_endpoints(float* out, const float* lat, const float* t, float eps, int B, int D, int mode, void* stream);
+int ideas_pair_prepare(void* y, const void* x, const int* box, const float* shift, const float* scale, int B, int C, int H, int W,
+                       int out_h, int out_w, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

@@ -2,11 +2,16 @@
 """Extraction accuracy (and FID) of a trained IDEAS checkpoint per jitter width: random bits -> containers -> 8-bit images -> bits.
 
     python evaluate.py [--sigma 1] [--delta 0 0.25 0.5] [--n_sample 50000] [--batch 32] [--container u8] [--seed 0]
-        [--inception inception_<name>.pkl --inception_weights pt_inception-2015-12-05-6726825d.pth] CHECKPOINT
+        [--attack SPEC [SPEC ...]] [--inception inception_<name>.pkl --inception_weights pt_inception-2015-12-05-6726825d.pth] CHECKPOINT
 
 Prints one line per delta, ``sigma=1 delta=25% ACC: 0.9999 FID: 15.56``.  The FID is printed only when both inception arguments are
 given: ``--inception`` is the pickle calc_inception.py wrote for the dataset, ``--inception_weights`` pytorch-fid's FID Inception state
 dict (not shipped); it is computed as fid.py does, on the containers the receiver sees.  ``--container float`` skips the 8-bit file.
+
+``--attack`` sends the 8-bit containers through a channel before the receiver sees them (``ideas_amd.attacks``): ``none``, ``jpeg:Q``
+(quality 1..100), ``noise:S`` (Gaussian, S in 8-bit levels), ``sp:P`` (salt and pepper, fraction P), ``gain:G``, ``offset:D``, or a
+chain such as ``noise:3+jpeg:75``.  One line per attack and delta, ``sigma=1 delta=25% attack=jpeg:75 ACC: 0.9871``; the generator
+is re-seeded for every line, so every attack sees the same messages and textures.
 """
 import argparse
 import pickle
@@ -22,12 +27,25 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=32)
     parser.add_argument("--container", choices=("u8", "float"), default="u8")
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--attack", type=str, nargs="+", default=None, metavar="SPEC",
+                        help="channel attacks on the 8-bit container: none, jpeg:Q, noise:S, sp:P, gain:G, offset:D, chained with +")
     parser.add_argument("--inception", type=str, default=None, help="dataset statistics written by calc_inception.py")
     parser.add_argument("--inception_weights", type=str, default=None, help="pt_inception-2015-12-05-6726825d.pth (pytorch-fid)")
-    parser.add_argument("ckpt", metavar="CHECKPOINT")
+    parser.add_argument("ckpt", metavar="CHECKPOINT", nargs="?")
     opt = parser.parse_args(argv)
+    if opt.ckpt is None and opt.attack and len(opt.attack) > 1:
+        opt.ckpt = opt.attack.pop()                           # "--attack none jpeg:75 CHECKPOINT": the list took the positional
+    if opt.ckpt is None:
+        parser.error("the following arguments are required: CHECKPOINT")
     if (opt.inception is None) != (opt.inception_weights is None):
         parser.error("--inception and --inception_weights go together")
+    from ideas_amd import attacks as attacks_mod
+    try:
+        attacks = [None] if opt.attack is None else [attacks_mod.parse(a) for a in opt.attack]
+    except ValueError as e:
+        parser.error(str(e))
+    if opt.attack is not None and opt.container != "u8":
+        parser.error("--attack acts on the 8-bit container: it needs --container u8")
 
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs a GPU (ideas_amd has no CPU path)")
@@ -45,14 +63,17 @@ def main(argv=None):
         inception = InceptionV3([3], normalize_input=False, weights=opt.inception_weights).to(device)
         with open(opt.inception, "rb") as f:
             embeds = pickle.load(f)
-    for delta in opt.delta:
-        gen = torch.Generator(device=device).manual_seed(opt.seed)
-        res = stego.evaluate(models, args, opt.sigma, delta, opt.n_sample, opt.batch, gen, container=opt.container, inception=inception)
-        line = f"sigma={opt.sigma} delta={delta * 100:g}% ACC: {res['acc']:.4f}"
-        if inception is not None:
-            stats = res["stats"]
-            line += f" FID: {calc_fid(stats.mean(), stats.cov(), embeds['mean'], embeds['cov']):.2f}"
-        print(line)
+    for attack in attacks:
+        for delta in opt.delta:
+            gen = torch.Generator(device=device).manual_seed(opt.seed)
+            res = stego.evaluate(models, args, opt.sigma, delta, opt.n_sample, opt.batch, gen, container=opt.container,
+                                 inception=inception, attack=attack)
+            line = f"sigma={opt.sigma} delta={delta * 100:g}%" + ("" if attack is None else f" attack={attack.name}")
+            line += f" ACC: {res['acc']:.4f}"
+            if inception is not None:
+                stats = res["stats"]
+                line += f" FID: {calc_fid(stats.mean(), stats.cov(), embeds['mean'], embeds['cov']):.2f}"
+            print(line)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,84 @@
+"""Channel attacks on the 8-bit container, on the HIP kernels of csrc/attack.hip: what a container suffers between sender and receiver.
+
+    jpeg_roundtrip(u8, quality)   a baseline-JPEG (4:4:4) encode and decode in one launch -- the model is stated step by step in
+                                  include/ideas_hip.h and restated in numpy by tests/attacks_ref.py
+    pixel_attack(u8, ...)         intensity (gain, offset), additive Gaussian noise (sigma) and salt and pepper (sp) in one launch
+
+Both take and return the uint8 ``[B, H, W, C]`` bytes of ``quantize_image`` (C = 1 or 3) together with ``y``, float32 ``[B, C, H, W]``
+in channels_last memory: bitwise ``data.u8_to_f32`` of the returned bytes, the image a receiver decodes.  Device tensors only (no CPU
+branch); forward-only.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .. import _lib
+
+
+def _bytes(u8: torch.Tensor, what: str) -> torch.Tensor:
+    _lib.require_cuda(u8)
+    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] not in (1, 3):
+        raise RuntimeError(f"{what} expects uint8 [B, H, W, C] with C = 1 or 3, got {u8.dtype} {tuple(u8.shape)}")
+    return u8.contiguous()
+
+
+def _outputs(u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    b, h, w, c = u8.shape
+    return torch.empty_like(u8), torch.empty((b, c, h, w), device=u8.device, dtype=torch.float32, memory_format=torch.channels_last)
+
+
+def jpeg_roundtrip(u8: torch.Tensor, quality: int, return_coef: bool = False):
+    """``u8`` through a JPEG file of ``quality`` (1..100, the IJG scale; 4:4:4, no chroma subsampling) -> ``(u8, y)``, or
+    ``(u8, y, coef)`` with ``return_coef``: the quantised DCT coefficients int16 ``[B, C, ceil(H/8), ceil(W/8), 64]`` at index
+    ``8 u + v`` (u the vertical frequency; planes Y, Cb, Cr).  One launch."""
+    u8 = _bytes(u8, "jpeg_roundtrip")
+    if int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise RuntimeError(f"jpeg_roundtrip: quality must be an integer in 1..100, got {quality!r}")
+    b, h, w, c = u8.shape
+    out, y = _outputs(u8)
+    coef = torch.empty((b, c, (h + 7) // 8, (w + 7) // 8, 64), device=u8.device, dtype=torch.int16) if return_coef else None
+    if u8.numel():
+        rc = _lib.load().ideas_jpeg_roundtrip(_lib.ptr(out), _lib.ptr(y), _lib.ptr(coef), _lib.ptr(u8), b, c, h, w, int(quality),
+                                              _lib.stream_ptr())
+        _lib.check(rc, "ideas_jpeg_roundtrip")
+    return (out, y, coef) if return_coef else (out, y)
+
+
+def _draw(fn, shape, generator: Optional[torch.Generator], device) -> torch.Tensor:
+    """f32 draws on ``device``; a generator of another device (a CPU generator for a GPU run) draws there and the result is copied."""
+    if generator is None or generator.device.type == device.type:
+        return fn(shape, generator=generator, device=device, dtype=torch.float32)
+    return fn(shape, generator=generator, device=generator.device, dtype=torch.float32).to(device)
+
+
+def pixel_attack(u8: torch.Tensor, gain: float = 1.0, offset: float = 0.0, sigma: float = 0.0, sp: float = 0.0,
+                 noise: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
+                 generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``r = trunc(clamp((x - 127.5) * gain + 127.5 + offset + sigma * noise + 0.5, 0, 255))``, every step one f32 operation in that
+    order, then salt and pepper: a pixel with ``u < sp / 2`` becomes 0 and one with ``u >= 1 - sp / 2`` becomes 255, in every channel.
+    ``offset`` and ``sigma`` are in 8-bit levels.  ``noise`` (standard normal, ``[B, H, W, C]``) and ``u`` (U[0,1), ``[B, H, W]``)
+    make the draws explicit; without them they are drawn here on the device from ``generator``, the noise first, and only those that
+    are needed (``sigma != 0``, ``sp != 0``).  -> ``(u8, y)``.  One launch."""
+    u8 = _bytes(u8, "pixel_attack")
+    _lib.require_cuda(noise, u)
+    b, h, w, c = u8.shape
+    if noise is None and sigma != 0:
+        noise = _draw(torch.randn, (b, h, w, c), generator, u8.device)
+    if u is None and sp != 0:
+        u = _draw(torch.rand, (b, h, w), generator, u8.device)
+    if noise is not None:
+        if tuple(noise.shape) != (b, h, w, c):
+            raise RuntimeError(f"pixel_attack: noise must be [{b}, {h}, {w}, {c}], got {tuple(noise.shape)}")
+        noise = noise.detach().to(torch.float32).contiguous()
+    if u is not None:
+        if tuple(u.shape) != (b, h, w):
+            raise RuntimeError(f"pixel_attack: u must be [{b}, {h}, {w}], got {tuple(u.shape)}")
+        u = u.detach().to(torch.float32).contiguous()
+    out, y = _outputs(u8)
+    if u8.numel():
+        rc = _lib.load().ideas_pixel_attack(_lib.ptr(out), _lib.ptr(y), _lib.ptr(u8), _lib.ptr(noise), _lib.ptr(u), b, c, h, w,
+                                            float(gain), float(offset), float(sigma), float(sp), _lib.stream_ptr())
+        _lib.check(rc, "ideas_pixel_attack")
+    return out, y

@@ -144,16 +144,22 @@ def unframe(rows) -> bytes:
 # ---------------------------------------------------------------------------------------------------------------------- evaluation
 @torch.no_grad()
 def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, generator: Optional[torch.Generator] = None,
-             container: str = "u8", inception=None) -> dict:
+             container: str = "u8", inception=None, attack=None) -> dict:
     """Extraction accuracy over ``n_sample`` containers carrying random bits: ``n_sample // batch`` full batches and the remainder (a
     zero remainder is skipped).  Per batch, in this order of draws from ``generator``: the bits, the jitter, the texture codes.
     ``container``: ``"u8"`` sends every image through 8 bits (``quantize_image``), ``"float"`` hands the generator's output to the
     receiver unrounded.  With ``inception`` (``ideas_amd.inception.InceptionV3([3], normalize_input=False)``) the feature statistics of
-    the received containers are accumulated too (``fid.feature_statistics``).  One host synchronisation, at the end.
+    the received containers are accumulated too (``fid.feature_statistics``).  ``attack`` (``ideas_amd.attacks.parse(spec)``; None:
+    the lossless file) is the channel the 8-bit container travels through: the receiver sees
+    ``attack(quantize_image(images)[0], generator)[1]``, the attack's draws come after the texture codes of the same batch, and the
+    feature statistics are taken on what the receiver sees.  One host synchronisation, at the end.
 
-    Returns ``acc`` (1 - n_err / n_bits), ``n_bits``, ``n_err``, ``l1`` (mean |hat_Z - Z|) and ``stats`` (``fid.FeatureStats`` or None)."""
+    Returns ``acc`` (1 - n_err / n_bits), ``n_bits``, ``n_err``, ``l1`` (mean |hat_Z - Z|), ``stats`` (``fid.FeatureStats`` or None)
+    and ``attack`` (the attack's name or None)."""
     if container not in ("u8", "float"):
         raise ValueError(f"evaluate: container must be 'u8' or 'float', got {container!r}")
+    if attack is not None and container != "u8":
+        raise ValueError("evaluate: an attack acts on the 8-bit container; container must be 'u8'")
     if n_sample <= 0 or batch <= 0:
         raise ValueError("evaluate: n_sample and batch must be positive")
     device = next(models["G"].parameters()).device
@@ -167,7 +173,10 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
                 continue
             bits = random_bits(b, cap, generator, device)
             images, Z = hide(models, args, bits, sigma, delta, generator=generator)
-            received = S.quantize_image(images)[1] if container == "u8" else images
+            if attack is not None:
+                received = attack(S.quantize_image(images, dequantize=False)[0], generator)[1]
+            else:
+                received = S.quantize_image(images)[1] if container == "u8" else images
             _, hat_Z, n_err = extract(models, args, received, sigma, ref_bits=bits)
             err.add_(n_err.sum())
             l1.add_((hat_Z.float() - Z).abs().sum(dtype=torch.float64))
@@ -182,4 +191,4 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
     n_bits = n_sample * cap
     n_err = int(err.item())
     return {"acc": 1.0 - n_err / n_bits, "n_bits": n_bits, "n_err": n_err, "l1": float(l1.item()) / (n_sample * cap // int(sigma)),
-            "stats": stats}
+            "stats": stats, "attack": None if attack is None else attack.name}

@@ -630,6 +630,59 @@ int ideas_pair_prepare(void* y, const void* x, const int* box, const float* shif
                        int out_h, int out_w, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Channel attacks on the 8-bit container, csrc/attack.hip: what happens to the bytes ideas_image_f32_to_u8 wrote between sender and
+ * receiver.  x_u8 and out_u8 are uint8 [B][H][W][C], C = 1 or 3 (out_u8 must not overlap x_u8).  y (optional, float [B][H][W][C]) =
+ * (out_u8 / 255 - 0.5) / 0.5, bitwise what ideas_image_u8_to_f32(mean 0.5, std 0.5) makes of out_u8.
+ *
+ *   ideas_jpeg_roundtrip   a baseline-JPEG encode and decode at 4:4:4, without the entropy coder (which is lossless), in ONE launch,
+ *                          no global scratch buffer, no stores outside out_u8, y and coef.  coef (optional, int16
+ *                          [B][C][ceil(H/8)][ceil(W/8)][64]) receives the quantised coefficients of every block at index 8 u + v, u the
+ *                          vertical frequency.  The model:
+ *     1. Colour, encode side (C = 3), 16-bit fixed point in integers as the IJG library does it:
+ *            Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *            Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *            Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *        C = 1 has a Y plane only.  (The decimal forms 0.299 ... have exact ties on integer inputs; the result would depend on the
+ *        float type.)
+ *     2. Padding: H and W are padded up to multiples of 8 by replicating the last row and column (clamped coordinates at load time).
+ *     3. Forward DCT: level shift by 128, then the orthonormal 8x8 DCT-II
+ *            F(u,v) = 1/4 c(u) c(v) sum_i sum_j f(i,j) cos((2i+1) u pi / 16) cos((2j+1) v pi / 16),   c(0) = 1 / sqrt 2, else 1.
+ *     4. Quantiser: the Annex K luminance (Y) and chrominance (Cb, Cr) tables scaled by the IJG quality rule, s = 5000 / quality
+ *        (integer division) for quality < 50, else 200 - 2 quality;  T = clamp((base * s + 50) / 100, 1, 255);  quality in 1..100.
+ *        Rounding half away from zero:  q = sign(F) floor(|F| / T + 0.5).
+ *     5. The four rational coefficients (0,0), (0,4), (4,0), (4,4) are exactly S / 8 with S an integer signed sum of the samples
+ *        (signs + - - + + - - + along an axis with frequency 4).  They are quantised in integers: q = sign(S) ((|S| + 4 T) / (8 T)).
+ *        Exact ties are common there: every flat block has one.
+ *     6. Inverse: q T through the inverse DCT, + 128, floor(v + 0.5), clamp to 0..255.  The four rational coefficients contribute
+ *        an integer divided by 8, which enters the sum exactly (their scaling is the constant 1/8, not a product of two rounded
+ *        1 / (2 sqrt 2)): a block in which only those four survive comes out bit for bit.
+ *     7. Colour, decode side, integers again, each clamped to 0..255:
+ *            R = Y + (( 91881 (Cr-128) + 32768) >> 16)
+ *            G = Y + ((-22554 (Cb-128) - 46802 (Cr-128) + 32768) >> 16)
+ *            B = Y + ((116130 (Cb-128) + 32768) >> 16)
+ *        The other 60 coefficients of a block and the samples are f32 sums: they agree with exact arithmetic except within 1.5e-3 of
+ *        a rounding tie (in units of F / T and of a grey level; tests/attacks_ref.py derives the figure).
+ *     IDEAS_E_NULL: x_u8 or out_u8 is NULL.  IDEAS_E_SHAPE: B, H or W <= 0, C other than 1 or 3.  IDEAS_E_UNSUPPORTED: quality
+ *     outside 1..100.  With W % 8 == 0, x_u8 and out_u8 8-byte aligned and y 16-byte aligned a lane moves its 8 pixels as 8-byte
+ *     words and float4; any other placement goes byte by byte.
+ *
+ *   ideas_pixel_attack     intensity, additive Gaussian noise and salt and pepper in one streaming launch.  Each step is rounded to
+ *                          f32, no fused multiply-add:
+ *            v = ((float)x - 127.5f) * gain + 127.5f + offset              offset in 8-bit levels
+ *            v = v + sigma * noise                                          with noise: float [B][H][W][C], standard normal, drawn by
+ *                                                                           the caller; sigma in 8-bit levels
+ *            r = trunc(clamp(v + 0.5f, 0, 255))                             a NaN gives 0
+ *            r = 0 in every channel where u < sp / 2,  255 in every channel where u >= 1 - sp / 2
+ *                                                                           with u: float [B][H][W], U[0,1), one draw per pixel
+ *     noise may be NULL only with sigma == 0, u only with sp == 0 (IDEAS_E_NULL otherwise, and for x_u8 or out_u8).
+ *     IDEAS_E_SHAPE: B, H or W <= 0, C other than 1 or 3.  Four pixels a lane (4-byte words of bytes, float4 of noise, u and y) when
+ *     x_u8, out_u8 are 4-byte and noise, u, y 16-byte aligned; one pixel a thread otherwise.
+ * Every check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+int ideas_jpeg_roundtrip(void* out_u8, float* y, short* coef, const void* x_u8, int B, int C, int H, int W, int quality, void* stream);
+int ideas_pixel_attack(void* out_u8, float* y, const void* x_u8, const float* noise, const float* u, int B, int C, int H, int W,
+                       float gain, float offset, float sigma, float sp, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Time the JPEG round trip of the 8-bit container at (32, 256, 256, 3), quality 75: ``ideas_jpeg_roundtrip`` with the received image
+(one launch: the entry point on preallocated outputs, and through ``op.jpeg_roundtrip``) next to the obvious torch spelling of the same
+model -- blocks by reshape, two 8x8 matmuls, divide, round, and back -- which is what a user would otherwise write on the device.
+
+Device events around windows of ``--launches`` calls, warm-up, the variants alternating inside one process, median and spread of the
+per-call time.  The calls of a window rotate over ``--sets`` input tensors.  The kernel's time is also given as the bytes it must move,
+B*H*W*C*(1 + 1 + 4), over the measured HBM copy rate.  The results are compared at the timed size.  Needs a GPU.
+
+    python tools/bench_attack.py [--out profiles/attack_jpeg.txt] [--batch 32] [--size 256] [--quality 75] [--reps 20]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_MEASURED = 6.29e12        # bytes / s: float4 copy
+
+
+def torch_spelling(quality, device):
+    """The model in torch ops for H, W multiples of 8 and C = 3: float colour and float coefficients throughout (no integer ties)."""
+    import attacks_ref as R                            # the tables and the DCT matrix of the numpy restatement
+    T = torch.from_numpy(R.quant_tables(quality)[[0, 1, 1]]).float().view(1, 3, 1, 1, 8, 8).to(device)
+    D = torch.from_numpy(R.dct_matrix()).float().to(device)
+    fwd = torch.tensor([[0.299, 0.587, 0.114], [-0.168736, -0.331264, 0.5], [0.5, -0.418688, -0.081312]], device=device)
+    inv = torch.tensor([[1.0, 0.0, 1.402], [1.0, -0.344136, -0.714136], [1.0, 1.772, 0.0]], device=device)
+    off = torch.tensor([0.0, 128.0, 128.0], device=device)
+
+    def run(u8):
+        b, h, w, _ = u8.shape
+        ycc = (u8.float() @ fwd.T + off).round().clamp(0, 255)
+        blk = (ycc - 128).permute(0, 3, 1, 2).reshape(b, 3, h // 8, 8, w // 8, 8).permute(0, 1, 2, 4, 3, 5)
+        F = D @ blk @ D.T
+        q = torch.sign(F) * torch.floor(F.abs() / T + 0.5)
+        rec = (D.T @ (q * T) @ D + 128 + 0.5).floor().clamp(0, 255)
+        ycc = rec.permute(0, 1, 2, 4, 3, 5).reshape(b, 3, h, w).permute(0, 2, 3, 1)
+        out = ((ycc - off) @ inv.T + 0.5).floor().clamp(0, 255).to(torch.uint8)
+        return out, ((out.float() / 255 - 0.5) / 0.5).permute(0, 3, 1, 2)
+    return run
+
+
+def window_ms(fn, xs, launches):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(launches):
+        fn(xs[i % len(xs)])
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / launches
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attack_jpeg.txt"))
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--quality", type=int, default=75)
+    ap.add_argument("--sets", type=int, default=48)
+    ap.add_argument("--launches", type=int, default=48)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_attack needs a GPU")
+    from ideas_amd import _lib
+    from ideas_amd.op import jpeg_roundtrip
+
+    b, r, q = args.batch, args.size, args.quality
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    # smooth plus grain, as a generated image is: a random field at 1/8 resolution, upsampled, with +-8 levels of noise
+    xs = []
+    for _ in range(args.sets):
+        low = torch.rand(b, 3, r // 8, r // 8, device="cuda", generator=gen)
+        img = torch.nn.functional.interpolate(low, size=(r, r), mode="bilinear", align_corners=False) * 255
+        img = img + (torch.rand(b, 3, r, r, device="cuda", generator=gen) - 0.5) * 16
+        xs.append(img.clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous())
+    n = b * 3 * r * r
+    out = torch.empty(b, r, r, 3, device="cuda", dtype=torch.uint8)
+    y = torch.empty(b, r, r, 3, device="cuda", dtype=torch.float32)
+    entry, stream = _lib.load().ideas_jpeg_roundtrip, _lib.stream_ptr()
+
+    def kernel_raw(x):                                # the entry point alone: outputs allocated once, no wrapper
+        entry(out.data_ptr(), y.data_ptr(), None, x.data_ptr(), b, 3, r, r, q, stream)
+
+    def op(x):
+        return jpeg_roundtrip(x, q)
+
+    spelled = torch_spelling(q, "cuda")
+    variants = (("kernel", kernel_raw), ("op", op), ("torch_ops", spelled))
+    for _ in range(args.warmup):
+        for _, fn in variants:
+            window_ms(fn, xs, args.launches)
+    torch.cuda.synchronize()
+    ts = {name: [] for name, _ in variants}
+    for _ in range(args.reps):
+        for name, fn in variants:
+            ts[name].append(window_ms(fn, xs, args.launches))
+    (u_a, y_a), (u_b, _) = op(xs[0]), spelled(xs[0])
+    kernel_raw(xs[0])
+    raw_same = bool(torch.equal(out, u_a)) and bool(torch.equal(y, y_a.permute(0, 2, 3, 1)))
+    d = (u_a.int() - u_b.int()).abs()
+    moved = n * (1 + 1 + 4)
+    lines = ["container -> JPEG quality %d (4:4:4) -> received image, (%d, %d, %d, 3) uint8; per-call ms over windows of %d calls rotating over "
+             "%d inputs (%.0f MiB), median of %d alternating windows [min .. max]"
+             % (q, b, r, r, args.launches, args.sets, args.sets * n / 2 ** 20, args.reps)]
+    for name, _ in variants:
+        v = ts[name]
+        lines.append("%-9s %8.4f  [%8.4f .. %8.4f]" % (name, statistics.median(v), min(v), max(v)))
+    t = statistics.median(ts["kernel"]) * 1e-3
+    lines.append("kernel: %d bytes moved (B*H*W*C*(1+1+4): bytes in, bytes out, the received image) -> %.2f TB/s = %.0f %% of the measured "
+                 "HBM copy rate (6.29 TB/s; the window includes the launch gaps); the bytes alone, %d each way, are %.0f %% of that time"
+                 % (moved, moved / t / 1e12, 100 * moved / t / HBM_MEASURED, n, 100 * (2 * n / HBM_MEASURED) / t))
+    lines.append("torch_ops / kernel: %.1fx; kernel == op: %s; torch_ops (float colour, f32 matmuls) vs op: %.3f %% of the bytes differ, "
+                 "largest difference %d levels"
+                 % (statistics.median(ts["torch_ops"]) / statistics.median(ts["kernel"]), raw_same, 100 * float((d > 0).float().mean()),
+                    int(d.max())))
+    print("\n".join(lines), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -1557,6 +1557,36 @@ def test_linear_kernels_vs_float64(case):
     assert all(torch.equal(a, b) for a, b in zip(got, got2))
 
 
+def test_linear_kernels_on_column_slices_of_wider_tensors():
+    """multi_linear on weights and an input that are column slices ``big[:, :K]`` of wider tensors (row stride 532 > K = 520, a
+    multiple of 4): op/linear.py must hand the kernels ``stride(0)``, not K -- forward, the summed input gradient (w's stride), the
+    weight gradients (x's stride).  The columns behind K hold random numbers, so a kernel that walks rows with K reads them; their
+    gradient must be exactly zero."""
+    from ideas_amd.op.linear import multi_linear
+    M, K, wide, ns = 33, 520, 532, (24, 8)
+    torch.manual_seed(M + K + wide)
+    bx = torch.randn(M, wide, dtype=torch.float64).requires_grad_(True)
+    bws = [torch.randn(n, wide, dtype=torch.float64).requires_grad_(True) for n in ns]
+    bs = [torch.randn(ns[0], dtype=torch.float64).requires_grad_(True), None]
+    scales, bmuls = [1 / math.sqrt(K), 1.5 / math.sqrt(K)], [1.0, 0.25]
+    ys = [s * (bx[:, :K] @ w[:, :K].t()) + (0 if b is None else bm * b) for w, b, s, bm in zip(bws, bs, scales, bmuls)]
+    gys = [torch.randn_like(y) for y in ys]
+    ref = torch.autograd.grad(ys, [bx] + bws + [bs[0]], gys)
+    t = lambda v: None if v is None else v.detach().float().cuda().requires_grad_(True)
+    bxd, bwd, bd = t(bx), [t(w) for w in bws], [t(b) for b in bs]
+    xd, wd = bxd[:, :K], [w[:, :K] for w in bwd]
+    assert xd.stride(0) == wide and all(w.stride(0) == wide and not w.is_contiguous() for w in wd)
+    yd = multi_linear(xd, [(w, b, s, bm) for w, b, s, bm in zip(wd, bd, scales, bmuls)])
+    assert type(yd[0].grad_fn).__name__.startswith("_MultiLinear"), "the HIP kernels did not run"
+    for a, r in zip(yd, ys):
+        assert rel_err(a, r) < TOL
+    got = torch.autograd.grad(yd, [bxd] + bwd + [bd[0]], [g.float().cuda() for g in gys])
+    for a, r in zip(got, ref):
+        assert rel_err(a, r) < GTOL, (tuple(r.shape), rel_err(a, r))
+    for a in got[:3]:
+        assert float(a[:, K:].abs().max()) == 0.0
+
+
 def test_linear_double_backward_and_sink():
     """The HIP linear Function under create_graph (R1 through the discriminator heads, train.py:105-129): its backward re-expresses
     itself with differentiable ops, second derivatives equal the f64 composite; inside grad_sink the weight / bias gradients of a

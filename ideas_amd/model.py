@@ -24,6 +24,7 @@ from torch.nn import functional as F
 
 from .op.linear import equal_linear
 from .op import FusedLeakyReLU, conv2d, conv2d_bias_act, fused_leaky_relu, modulated_conv2d, upfirdn2d
+from .op.upfirdn2d import blur_pads
 
 CL = torch.channels_last
 _DISC_NAMES = ("ConvLayer", "ResBlock", "Discriminator")
@@ -204,14 +205,8 @@ class ModulatedConv2d(nn.Module):
         self.out_channel = out_channel
         self.upsample = upsample
         self.downsample = downsample
-        if upsample:
-            factor = 2
-            p = (len(blur_kernel) - factor) - (kernel_size - 1)
-            self.blur = Blur(blur_kernel, pad=((p + 1) // 2 + factor - 1, p // 2 + 1), upsample_factor=factor)
-        if downsample:
-            factor = 2
-            p = (len(blur_kernel) - factor) + (kernel_size - 1)
-            self.blur = Blur(blur_kernel, pad=((p + 1) // 2, p // 2))
+        if upsample or downsample:
+            self.blur = Blur(blur_kernel, pad=blur_pads(len(blur_kernel), kernel_size, up=upsample), upsample_factor=2 if upsample else 1)
         self.scale = 1 / math.sqrt(in_channel * kernel_size ** 2)
         self.padding = kernel_size // 2
         self.weight = nn.Parameter(modconv_weight_layout(torch.randn(1, out_channel, in_channel, kernel_size, kernel_size), upsample))

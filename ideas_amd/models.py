@@ -23,7 +23,7 @@ from .model import (CL, Blur, EqualConv2d, EqualLinear, ScaledLeakyReLU,
                     StyledConv_without_noise as StyledConv, styles_for)
 from .op import FusedLeakyReLU, conv2d, conv_transpose2d, upfirdn2d
 from .op.conv import down_pair, down_pair_ok, fork_conv2d
-from .op.upfirdn2d import fork_down2, upfirdn2d_up2_add
+from .op.upfirdn2d import blur_pads, fork_down2, upfirdn2d_up2_add
 from .precision import to_act, to_f32
 
 _INV_SQRT2 = 1.0 / math.sqrt(2)
@@ -55,15 +55,6 @@ class EqualConvTranspose2d(nn.Module):
         return f"{self.__class__.__name__}({i}, {o}, {k}, stride={self.stride}, padding={self.padding})"
 
 
-def _blur_pads(n_taps: int, kernel_size: int, up: bool):
-    factor = 2
-    if up:
-        p = (n_taps - factor) - (kernel_size - 1)
-        return (p + 1) // 2 + factor - 1, p // 2 + 1
-    p = (n_taps - factor) + (kernel_size - 1)
-    return (p + 1) // 2, p // 2
-
-
 class ConvLayer(nn.Sequential):
     """[Blur] -> (ConvT -> Blur | [ReflectionPad] -> Conv) -> [FusedLeakyReLU | Tanh | ScaledLeakyReLU]."""
 
@@ -73,11 +64,11 @@ class ConvLayer(nn.Sequential):
         conv_bias = bias and not activate
         conv_pad, stride = 0, 1
         if downsample:
-            mods.append(Blur(blur_kernel, pad=_blur_pads(len(blur_kernel), kernel_size, up=False)))
+            mods.append(Blur(blur_kernel, pad=blur_pads(len(blur_kernel), kernel_size, up=False)))
             stride = 2
         if upsample:
             mods.append(EqualConvTranspose2d(in_channel, out_channel, kernel_size, padding=0, stride=2, bias=conv_bias))
-            mods.append(Blur(blur_kernel, pad=_blur_pads(len(blur_kernel), kernel_size, up=True)))
+            mods.append(Blur(blur_kernel, pad=blur_pads(len(blur_kernel), kernel_size, up=True)))
         else:
             if not downsample:
                 half = (kernel_size - 1) // 2

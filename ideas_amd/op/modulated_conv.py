@@ -1,4 +1,4 @@
-"""Modulated / demodulated 3x3 convolution without per-sample weights.
+"""Modulated / demodulated convolution without per-sample weights.
 
 Mirror of ``ModulatedConv2d.forward`` (stylegan2/model.py:236-277; the same-resolution and upsample branches IDEAS
 instantiates, models.py:143-152, and the downsample branch of the layer library).  The reference materialises a [B*Cout, Cin, 3, 3] weight
@@ -10,8 +10,15 @@ so ONE implicit GEMM with the shared weight serves the whole batch: ``s`` scales
 is staged into LDS, ``d`` scales the accumulator in the epilogue (kernel: csrc/conv_igemm.hip).  The
 demodulation factor d[b,o] = rsqrt(sum_i s[b,i]^2 * wsq[o,i] + 1e-8), wsq = scale^2 * sum_k W^2, is a
 wavefront-shuffle reduction (csrc/modconv_aux.hip) instead of a pass over the per-sample weights; its derivative (to the style
-and to W) is folded into the backward of the conv Functions (ideas_demod_bwd, ideas_demod_wgrad).
+and to W) is folded into the backward of the conv Function (ideas_demod_bwd, ideas_demod_wgrad).
 Difference to the reference's association is f32-roundoff class (SURVEY.md §7 measured 1.8e-6 abs on |y|~4).
+
+One autograd Function, ``_ModConv``, owns all three modes (same, up, down), each with or without the demodulation, same and
+down also with bias + leaky-ReLU in the conv epilogue.  ``_mod_forward`` is the one place that picks the raw conv call of a mode
+(the no-grad ``resid`` path of ``modulated_conv2d`` goes through it too), and the one ``backward`` is six steps: activation
+prologue, the conv's input gradient with the two scales trading places (down: then the blur's adjoint), the two per-sample dots,
+``_style_grads``, and the weight gradient + ``_demod_wgrad`` under ``weight_grad``.  The mode picks the raw calls and the operand
+roles, nothing else.
 """
 from __future__ import annotations
 
@@ -29,7 +36,7 @@ from .conv import conv2d, conv_dgrad_raw, conv_fwd_raw, conv_transpose2d, conv_w
 from .conv_plan import ConvGeom, convT_out_size
 from . import conv_plan
 from . import scratch
-from .upfirdn2d import _geometry, blur_bias_act, upfirdn2d, upfirdn2d_raw
+from .upfirdn2d import _geometry, blur_bias_act, blur_pads, upfirdn2d, upfirdn2d_raw
 from .fused_act import bias_sink, fused_leaky_relu
 from .grad_sink import weight_grad
 
@@ -48,29 +55,25 @@ def pixel_dot(a: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _weight_sqsum(w: torch.Tensor, scale: float, dtype, entry: str, key: str) -> torch.Tensor:
+    def make():
+        cout, cin, kh, kw = w.shape
+        wsq = torch.empty((cout, cin), device=w.device, dtype=dtype)
+        _lib.check(getattr(_lib.load(), entry)(_lib.ptr(wsq), _lib.ptr(w), cout, cin, kh, kw, *w.stride(), float(scale * scale),
+                                               _lib.stream_ptr()), entry)
+        return wsq
+    return conv_plan.cached(w, (key, float(scale)), make)
+
+
 def weight_sqsum(w: torch.Tensor, scale: float) -> torch.Tensor:
     """wsq[o,i] = scale^2 * sum_k W[o,i,k]^2 (one kernel over the parameter in whatever strides it has; memoised per optimiser
     step like the other derived weights)."""
-    def make():
-        cout, cin, kh, kw = w.shape
-        wsq = torch.empty((cout, cin), device=w.device, dtype=torch.float32)
-        so, si, sky, skx = w.stride()
-        _lib.check(_lib.load().ideas_weight_sqsum(_lib.ptr(wsq), _lib.ptr(w), cout, cin, kh, kw, so, si, sky, skx, float(scale * scale),
-                                                  _lib.stream_ptr()), "ideas_weight_sqsum")
-        return wsq
-    return conv_plan.cached(w, ("wsq", float(scale)), make)
+    return _weight_sqsum(w, scale, torch.float32, "ideas_weight_sqsum", "wsq")
 
 
 def weight_sqsum_f64(w: torch.Tensor, scale: float) -> torch.Tensor:
     """The same table in double, for the backward's demodulation algebra (ideas_demod_bwd); memoised like the f32 one."""
-    def make():
-        cout, cin, kh, kw = w.shape
-        wsq = torch.empty((cout, cin), device=w.device, dtype=torch.float64)
-        so, si, sky, skx = w.stride()
-        _lib.check(_lib.load().ideas_weight_sqsum_f64(_lib.ptr(wsq), _lib.ptr(w), cout, cin, kh, kw, so, si, sky, skx, float(scale * scale),
-                                                      _lib.stream_ptr()), "ideas_weight_sqsum_f64")
-        return wsq
-    return conv_plan.cached(w, ("wsq64", float(scale)), make)
+    return _weight_sqsum(w, scale, torch.float64, "ideas_weight_sqsum_f64", "wsq64")
 
 
 def demod_raw(s: torch.Tensor, wsq: torch.Tensor, eps: float) -> torch.Tensor:
@@ -124,65 +127,6 @@ def _demod_wgrad(gw: torch.Tensor, w: torch.Tensor, gq: torch.Tensor, s: torch.T
     _lib.check(rc, "ideas_demod_wgrad")
 
 
-class _ModConv(Function):
-    """y = gain * d[b,o] * conv(s[b,i] * x, W)   (same-res, pad 1)  or the stride-2 transposed variant, with the demodulation
-    d = rsqrt(sum_i s^2 wsq + eps) (``demod``) computed and differentiated inside: the backward returns the complete style
-    gradient (direct + through d) and adds the through-d term to the weight gradient, 2 small kernels instead of ~20 tensor ops."""
-
-    @staticmethod
-    def forward(ctx, x, w, s, up: bool, gain: float, demod: bool, eps: float):
-        x = _nhwc(x)
-        s = s.contiguous()
-        d = demod_of(w, s, gain, eps) if demod else None
-        k = w.shape[2]
-        if up:
-            g = ConvGeom(k, k, 2, 0, False)
-            wt = w.transpose(0, 1)  # read as conv weight [O'=Cin, I'=Cout]
-            y = conv_dgrad_raw(x, wt, g, convT_out_size(x.shape[2], x.shape[3], g), gain, lin=s, lout=d)
-        else:
-            g = ConvGeom(k, k, 1, k // 2, False)
-            y = conv_fwd_raw(x, w, g, gain, lin=s, lout=d)
-        ctx.g, ctx.up, ctx.gain, ctx.has_d, ctx.eps = g, up, gain, d is not None, eps
-        ctx.save_for_backward(x, w, s, d if d is not None else s.new_zeros(0), y)
-        return y
-
-    @staticmethod
-    @once_differentiable          # raw kernels below: a create_graph pass must use second_order() and raises otherwise
-    def backward(ctx, gy):
-        x, w, s, d, y = ctx.saved_tensors
-        d = d if ctx.has_d else None
-        g, gain = ctx.g, ctx.gain
-        gy = _nhwc(gy)
-        need_x, need_w, need_s = ctx.needs_input_grad[:3]
-        gx = gw = gs = gq = None
-        if need_x or need_s:
-            if ctx.up:
-                gx = conv_fwd_raw(gy, w.transpose(0, 1), g, gain, lin=d, lout=s)
-            else:
-                gx = conv_dgrad_raw(gy, w, g, (x.shape[2], x.shape[3]), gain, lin=d, lout=s)
-        if need_s or (need_w and d is not None):
-            dot_s = pixel_dot(x, gx) if need_s else scratch.zeros(tuple(s.shape), s.device, torch.float64)
-            gs, gq = _style_grads(dot_s, pixel_dot(gy, y) if d is not None else None, s, d, w, gain, ctx.eps)
-        if need_w:
-            if ctx.up:
-                wt_shape = (w.shape[1], w.shape[0], w.shape[2], w.shape[3])
-
-                def grad(out):
-                    r = conv_wgrad_raw(x, gy, g, wt_shape, gain, lin=d, lout=s,
-                                       out=None if out is None else out.transpose(0, 1)).transpose(0, 1)
-                    if gq is not None:
-                        _demod_wgrad(r, w, gq, s, gain)
-                    return r
-            else:
-                def grad(out):
-                    r = conv_wgrad_raw(gy, x, g, tuple(w.shape), gain, lin=s, lout=d, out=out)
-                    if gq is not None:
-                        _demod_wgrad(r, w, gq, s, gain)
-                    return r
-            gw = weight_grad(w, grad, x, gy, s, d, gq)
-        return (gx if need_x else None), gw, (gs if need_s else None), None, None, None, None
-
-
 def act_bwd_dot(gy: torch.Tensor, out: torch.Tensor, bias: torch.Tensor, alpha: float, act_gain: float, bias_grad_into=None):
     """(g_pre, bias_grad[C], dot[B,C] float64) from the incoming gradient and the saved post-activation output.  ``bias_grad_into``: add
     the bias gradient into that f32 [C] buffer (the parameter's .grad) instead of returning a fresh one (returns None for it)."""
@@ -200,117 +144,119 @@ def act_bwd_dot(gy: torch.Tensor, out: torch.Tensor, bias: torch.Tensor, alpha: 
     return gpre, (None if bias_grad_into is not None else bg), dot
 
 
-class _ModConvAct(Function):
-    """Same-resolution demodulated conv with bias + leaky-ReLU in the epilogue (StyledConv_without_noise,
-    stylegan2/model.py:371-377).  Only the post-activation output is kept for the backward; the pre-activation
-    needed by d(demod) is recovered inside the fused backward-prologue kernel (ideas_act_bwd_dot)."""
-
-    @staticmethod
-    def forward(ctx, x, w, s, b, gain: float, slope: float, act_gain: float, eps: float):
-        x = _nhwc(x)
-        bias_param = b
-        s, b = s.contiguous(), b.contiguous()
-        d = demod_of(w, s, gain, eps)
-        k = w.shape[2]
-        g = ConvGeom(k, k, 1, k // 2, False)
-        y = conv_fwd_raw(x, w, g, gain, lin=s, lout=d, bias=b, act=True, act_gain=act_gain, alpha=slope)
-        ctx.g, ctx.gain, ctx.slope, ctx.act_gain, ctx.eps = g, gain, slope, act_gain, eps
-        ctx.bias_ref = bias_param
-        ctx.save_for_backward(x, w, s, d, b, y)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, w, s, d, b, y = ctx.saved_tensors
-        g, gain = ctx.g, ctx.gain
-        need_x, need_w, need_s, need_b = ctx.needs_input_grad[:4]
-        gpre, gb, dot_d = act_bwd_dot(gy, y, b, ctx.slope, ctx.act_gain, bias_grad_into=bias_sink(ctx.bias_ref) if need_b else None)
-        gx = gw = gs = gq = None
-        if need_x or need_s:
-            gx = conv_dgrad_raw(gpre, w, g, (x.shape[2], x.shape[3]), gain, lin=d, lout=s)
-        if need_s or need_w:
-            dot_s = pixel_dot(x, gx) if need_s else scratch.zeros(tuple(s.shape), s.device, torch.float64)
-            gs, gq = _style_grads(dot_s, dot_d, s, d, w, gain, ctx.eps)
-        if need_w:
-            def grad(out):
-                r = conv_wgrad_raw(gpre, x, g, tuple(w.shape), gain, lin=s, lout=d, out=out)
-                _demod_wgrad(r, w, gq, s, gain)
-                return r
-            gw = weight_grad(w, grad, gpre, x, s, d, gq)
-        return (gx if need_x else None), gw, (gs if need_s else None), (gb if need_b else None), None, None, None, None
+def _mod_geom(mode: str, k: int) -> ConvGeom:
+    """The conv of each mode: same-resolution (pad k // 2); up: stride 2, run as the input gradient of that conv; down: stride 2
+    behind the Blur -- a 1x1 kernel: unstrided behind the decimating FIR, as ConvLayer's skip branch."""
+    if mode == "same":
+        return ConvGeom(k, k, 1, k // 2, False)
+    return ConvGeom(k, k, 1 if (mode == "down" and k == 1) else 2, 0, False)
 
 
-class _ModConvDown(Function):
-    """The downsample branch (stylegan2/model.py:210-216, 263-269): Blur, then the stride-2 modulated conv, re-associated like the
-    other branches -- the blur is linear and per channel, so the style scales the BLURRED activation:
+def _down_blur(x, fir, k: int, pad2):
+    """(down, pad4, blurred size, the adjoint's pads) of the down mode's Blur: ``upfirdn2d(x, fir, down=down, pad=pad2)``."""
+    down = 2 if k == 1 else 1
+    return (down,) + _geometry((x.shape[2], x.shape[3]), fir, 1, down, pad2)
+
+
+def _mod_forward(x, w, s, d, mode: str, fir, pad2, gain: float, bias=None, slope: float = 0.2, act_gain: float = 1.0, resid=None,
+                 want_xb: bool = False):
+    """(y, xb) of one modulated conv from its scales ``s`` [B, Cin] / ``d`` [B, Cout] or None: the only place that picks the raw
+    call.  ``bias``: bias + leaky-ReLU in the conv epilogue (same and down).  ``xb``: the down mode's blurred tensor (None where
+    the fused launch was not asked for it), None in the other modes."""
+    k = w.shape[2]
+    g = _mod_geom(mode, k)
+    epi = dict(lin=s, lout=d, bias=bias, act=bias is not None, act_gain=act_gain, alpha=slope)
+    if mode == "same":                                              # stylegan2/model.py:271-275
+        return conv_fwd_raw(x, w, g, gain, resid=resid, **epi), None
+    if mode == "up":                                                # :250-260; w.transpose: read as conv weight [O'=Cin, I'=Cout]
+        return conv_dgrad_raw(x, w.transpose(0, 1), g, convT_out_size(x.shape[2], x.shape[3], g), gain, lin=s, lout=d), None
+    # down (:263-269): ONE kernel (ideas_b3_blur_conv_s2_mod) where ``mod_blur_conv_ok`` admits the shape (looked up through the
+    # module at call time), else the blur kernel + the scaled stride-2 conv
+    if k == 3 and _conv.mod_blur_conv_ok(x, w, fir, pad2, want_xb=want_xb):
+        return _conv.blur_conv_s2_raw(x, w, fir, pad2, gain, want_xb=want_xb, **epi)
+    down, pad4, bhw, _ = _down_blur(x, fir, k, pad2)
+    xb = upfirdn2d_raw(x, fir, (1, 1), (down, down), pad4, bhw, flip=True)
+    return conv_fwd_raw(xb, w, g, gain, **epi), xb
+
+
+class _ModConv(Function):
+    """y = gain * d[b,o] * conv(s[b,i] * x, W) in one of three modes -- ``same`` (pad k // 2), ``up`` (the stride-2 transposed
+    variant; its Blur follows outside) and ``down`` (stylegan2/model.py:210-216, 263-269: Blur, then the stride-2 conv) -- with the
+    demodulation d = rsqrt(sum_i s^2 wsq + eps) (``demod``) computed and differentiated inside: the backward returns the complete
+    style gradient (direct + through d) and adds the through-d term to the weight gradient, 2 small kernels instead of ~20 tensor ops.
+
+    ``b`` (same and down): bias + leaky-ReLU in the conv epilogue (StyledConv_without_noise, stylegan2/model.py:371-377).  Only the
+    post-activation output is kept for the backward; the pre-activation needed by d(demod) is recovered inside the fused
+    backward-prologue kernel (ideas_act_bwd_dot).
+
+    Down is re-associated like the other modes -- the blur is linear and per channel, so the style scales the BLURRED activation:
 
         y[b,o] = gain * d[b,o] * sum_{i,k} W[o,i,k] * (s[b,i] * xb[b,i, 2. + k]),   xb = upfirdn2d(x, fir, pad2)
 
-    optionally with bias + leaky-ReLU in the conv epilogue (``b``).  Forward: ONE kernel (ideas_b3_blur_conv_s2_mod) where
-    ``mod_blur_conv_ok`` admits the shape, else the blur kernel + the scaled stride-2 conv (a 1x1 kernel: the decimating FIR + an
-    unstrided 1x1 conv, as ConvLayer's skip branch).  The blurred tensor is kept only for the weight gradient (the fused kernel's side
-    output); the style gradient's direct term is taken on the raw side, <x, B^T g> = <B x, g> per sample and channel."""
+    The blurred tensor is kept only for the weight gradient (the fused kernel's side output); the style gradient's direct term is
+    taken on the raw side, <x, B^T g> = <B x, g> per sample and channel."""
 
     @staticmethod
-    def forward(ctx, x, w, s, b, fir, pad2, gain: float, demod: bool, eps: float, slope: float, act_gain: float):
+    def forward(ctx, x, w, s, b, mode: str, fir, pad2, gain: float, demod: bool, eps: float, slope: float, act_gain: float):
         x = _nhwc(x)
-        bias_param = b
         s = s.contiguous()
-        act = b is not None
-        if act:
+        ctx.bias_ref = b                      # the parameter (gradient sink), not its contiguous copy
+        if b is not None:
             b = b.contiguous()
         d = demod_of(w, s, gain, eps) if demod else None
-        k = w.shape[2]
         need_w = ctx.needs_input_grad[1]
-        down = 2 if k == 1 else 1
-        pad4, bhw, g_pad = _geometry((x.shape[2], x.shape[3]), fir, 1, down, pad2)
-        g = ConvGeom(k, k, 1 if k == 1 else 2, 0, False)
-        if k == 3 and _conv.mod_blur_conv_ok(x, w, fir, pad2, want_xb=need_w):
-            y, xb = _conv.blur_conv_s2_raw(x, w, fir, pad2, gain, bias=b, act=act, act_gain=act_gain, alpha=slope, want_xb=need_w,
-                                           lin=s, lout=d)
-        else:
-            xb = upfirdn2d_raw(x, fir, (1, 1), (down, down), pad4, bhw, flip=True)
-            y = conv_fwd_raw(xb, w, g, gain, lin=s, lout=d, bias=b, act=act, act_gain=act_gain, alpha=slope)
-        ctx.g, ctx.gain, ctx.has_d, ctx.eps, ctx.act, ctx.slope, ctx.act_gain = g, gain, d is not None, eps, act, slope, act_gain
-        ctx.down, ctx.bhw, ctx.g_pad = down, bhw, g_pad
-        ctx.bias_ref = bias_param
-        none = s.new_zeros(0)
-        keep_y = act or d is not None         # read by the activation backward / the demodulation term only
-        ctx.save_for_backward(x, w, s, d if d is not None else none, y if keep_y else none, xb if need_w else none,
-                              b if act else none, fir)
+        y, xb = _mod_forward(x, w, s, d, mode, fir, pad2, gain, b, slope, act_gain, want_xb=need_w)
+        ctx.mode, ctx.pad2, ctx.gain, ctx.eps, ctx.slope, ctx.act_gain = mode, pad2, gain, eps, slope, act_gain
+        keep = dict(x=x, w=w, s=s, fir=fir, d=d, b=b,
+                    y=y if (b is not None or d is not None) else None,     # read by the activation backward / the demodulation term only
+                    xb=xb if need_w else None)
+        ctx.names = [n for n, t in keep.items() if t is not None]
+        ctx.save_for_backward(*(keep[n] for n in ctx.names))
         return y
 
     @staticmethod
-    @once_differentiable
+    @once_differentiable          # raw kernels below: a create_graph pass must use second_order() and raises otherwise
     def backward(ctx, gy):
-        x, w, s, d, y, xb, b, fir = ctx.saved_tensors
-        d = d if ctx.has_d else None
-        g, gain = ctx.g, ctx.gain
+        t = dict(zip(ctx.names, ctx.saved_tensors))
+        x, w, s, d, b, y = t["x"], t["w"], t["s"], t.get("d"), t.get("b"), t.get("y")
+        mode, gain = ctx.mode, ctx.gain
+        g = _mod_geom(mode, w.shape[2])
         need_x, need_w, need_s, need_b = ctx.needs_input_grad[:4]
         gb = dot_d = None
-        if ctx.act:
+        if b is not None:
             gpre, gb, dot_d = act_bwd_dot(gy, y, b, ctx.slope, ctx.act_gain, bias_grad_into=bias_sink(ctx.bias_ref) if need_b else None)
         else:
             gpre = gy = _nhwc(gy)
         gx = gw = gs = gq = None
-        if need_x or need_s:
-            gxb = conv_dgrad_raw(gpre, w, g, ctx.bhw, gain, lin=d, lout=s)
-            gx = upfirdn2d_raw(gxb, fir, (ctx.down, ctx.down), (1, 1), ctx.g_pad, (x.shape[2], x.shape[3]), flip=False)
+        if need_x or need_s:                  # the conv's input gradient: the per-sample scales trade places
+            if mode == "up":
+                gx = conv_fwd_raw(gpre, w.transpose(0, 1), g, gain, lin=d, lout=s)
+            elif mode == "same":
+                gx = conv_dgrad_raw(gpre, w, g, (x.shape[2], x.shape[3]), gain, lin=d, lout=s)
+            else:                             # ... and the blur's adjoint
+                down, _, bhw, g_pad = _down_blur(x, t["fir"], w.shape[2], ctx.pad2)
+                gx = conv_dgrad_raw(gpre, w, g, bhw, gain, lin=d, lout=s)
+                gx = upfirdn2d_raw(gx, t["fir"], (down, down), (1, 1), g_pad, (x.shape[2], x.shape[3]), flip=False)
         if need_s or (need_w and d is not None):
             dot_s = pixel_dot(x, gx) if need_s else scratch.zeros(tuple(s.shape), s.device, torch.float64)
             if d is not None and dot_d is None:
                 dot_d = pixel_dot(gy, y)
             gs, gq = _style_grads(dot_s, dot_d, s, d, w, gain, ctx.eps)
         if need_w:
+            xin = t["xb"] if mode == "down" else x            # what the conv read
+
             def grad(out):
-                r = conv_wgrad_raw(gpre, xb, g, tuple(w.shape), gain, lin=s, lout=d, out=out)
+                if mode == "up":              # the transposed conv's weight [Cin, Cout]: operand roles and scales trade places
+                    r = conv_wgrad_raw(xin, gpre, g, (w.shape[1], w.shape[0], w.shape[2], w.shape[3]), gain, lin=d, lout=s,
+                                       out=None if out is None else out.transpose(0, 1)).transpose(0, 1)
+                else:
+                    r = conv_wgrad_raw(gpre, xin, g, tuple(w.shape), gain, lin=s, lout=d, out=out)
                 if gq is not None:
                     _demod_wgrad(r, w, gq, s, gain)
                 return r
-            gw = weight_grad(w, grad, gpre, xb, s, d, gq)
-        return ((gx if need_x else None), gw, (gs if need_s else None), (gb if (ctx.act and need_b) else None),
-                None, None, None, None, None, None, None)
+            gw = weight_grad(w, grad, gpre, xin, s, d, gq)
+        return ((gx if need_x else None), gw, (gs if need_s else None), (gb if need_b else None),
+                None, None, None, None, None, None, None, None)
 
 
 _SECOND_ORDER = [False]
@@ -331,18 +277,12 @@ class second_order:
         _SECOND_ORDER[0] = self.prev
 
 
-def _down_pad(fir: torch.Tensor, k: int):
-    """The pads of the downsample branch's Blur (stylegan2/model.py:212-216)."""
-    p = (fir.shape[0] - 2) + (k - 1)
-    return (p + 1) // 2, p // 2
-
-
 def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale, downsample=False):
     cout, cin, k, _ = w.shape
     scale = 1.0 / math.sqrt(cin * k * k)
     xs = x * style.view(style.shape[0], cin, 1, 1)
     if downsample:
-        y = conv2d(upfirdn2d(xs, fir, pad=_down_pad(fir, k)), w, None, stride=2, padding=0, gain=scale)
+        y = conv2d(upfirdn2d(xs, fir, pad=blur_pads(fir.shape[0], k, up=False)), w, None, stride=2, padding=0, gain=scale)
     elif upsample:
         y = conv_transpose2d(xs, w.transpose(0, 1), None, stride=2, gain=scale)
     else:
@@ -352,8 +292,7 @@ def _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act
         d = torch.rsqrt((style * style) @ wsq.t() + eps)
         y = y * d.view(d.shape[0], cout, 1, 1)
     if upsample:
-        p = (fir.shape[0] - 2) - (k - 1)
-        y = upfirdn2d(y, fir, pad=((p + 1) // 2 + 1, p // 2 + 1))
+        y = upfirdn2d(y, fir, pad=blur_pads(fir.shape[0], k, up=True))
     if act_bias is not None:
         y = fused_leaky_relu(y, act_bias, negative_slope, act_scale)
     return y
@@ -371,9 +310,10 @@ def modulated_conv2d(x: torch.Tensor, weight: torch.Tensor, style: torch.Tensor,
     if upsample and downsample:
         raise ValueError("modulated_conv2d: upsample and downsample are exclusive")
     _lib.require_cuda(x, weight, style)
+    mode = "down" if downsample else "up" if upsample else "same"
+    if mode != "same" and fir is None:
+        raise RuntimeError(f"modulated_conv2d({mode}sample=True) needs the blur FIR")
     if downsample:
-        if fir is None:
-            raise RuntimeError("modulated_conv2d(downsample=True) needs the blur FIR")
         if resid is not None:
             raise RuntimeError("modulated_conv2d(resid=...) is the no-grad fast path of the fused same-resolution conv")
         _lib.require_cuda(fir, act_bias)
@@ -385,31 +325,22 @@ def modulated_conv2d(x: torch.Tensor, weight: torch.Tensor, style: torch.Tensor,
     if _SECOND_ORDER[0] and torch.is_grad_enabled() and resid is None:
         return _modulated_conv2d_composite(x, w, style, demodulate, upsample, fir, eps, act_bias, negative_slope, act_scale, downsample)
     scale = 1.0 / math.sqrt(cin * k * k)
-    if downsample:
-        fuse = act_bias is not None and demodulate and cout % 4 == 0
-        y = _ModConvDown.apply(x, w, style, act_bias if fuse else None, fir, _down_pad(fir, k), scale, bool(demodulate), float(eps),
-                               float(negative_slope), float(act_scale))
-        return y if (fuse or act_bias is None) else fused_leaky_relu(y, act_bias, negative_slope, act_scale)
+    pad2 = blur_pads(fir.shape[0], k, up=upsample) if mode != "same" else None
+    # bias + leaky-ReLU ride in the conv epilogue of the same and down modes; elsewhere the activation follows as its own op
     fuse_act = act_bias is not None and not upsample and demodulate and cout % 4 == 0
     if resid is not None:
         if not fuse_act or torch.is_grad_enabled():
             raise RuntimeError("modulated_conv2d(resid=...) is the no-grad fast path of the fused same-resolution conv")
-        k_ = w.shape[2]
         style = style.contiguous()
         d = demod_raw(style, weight_sqsum(w, scale), eps)
-        return conv_fwd_raw(x, w, ConvGeom(k_, k_, 1, k_ // 2, False), scale, lin=style, lout=d,
-                            bias=act_bias.contiguous(), act=True, act_gain=float(act_scale), alpha=float(negative_slope),
-                            resid=resid, resid_gain=1.0)
-    if fuse_act:
-        return _ModConvAct.apply(x, w, style, act_bias, scale, float(negative_slope), float(act_scale), float(eps))
-    y = _ModConv.apply(x, w, style, upsample, scale, bool(demodulate), float(eps))
+        return _mod_forward(x, w, style, d, mode, None, None, scale, act_bias.contiguous(), float(negative_slope), float(act_scale),
+                            resid=resid)[0]
+    y = _ModConv.apply(x, w, style, act_bias if fuse_act else None, mode, *((fir, pad2) if downsample else (None, None)),
+                       scale, bool(demodulate), float(eps), float(negative_slope), float(act_scale))
     if upsample:
-        if fir is None:
-            raise RuntimeError("modulated_conv2d(upsample=True) needs the blur FIR")
-        p = (fir.shape[0] - 2) - (k - 1)
         if act_bias is not None:          # blur + bias + leaky-ReLU in one pass over the upsampled tensor
-            return blur_bias_act(y, fir, ((p + 1) // 2 + 1, p // 2 + 1), act_bias, negative_slope, act_scale)
-        y = upfirdn2d(y, fir, pad=((p + 1) // 2 + 1, p // 2 + 1))
-    if act_bias is not None:
+            return blur_bias_act(y, fir, pad2, act_bias, negative_slope, act_scale)
+        return upfirdn2d(y, fir, pad=pad2)
+    if act_bias is not None and not fuse_act:
         y = fused_leaky_relu(y, act_bias, negative_slope, act_scale)
     return y

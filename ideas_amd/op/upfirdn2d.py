@@ -124,6 +124,17 @@ def blur_bias_act(x: torch.Tensor, fir: torch.Tensor, pad, bias: torch.Tensor, n
     return _BlurBiasAct.apply(x, fir, (pad[0], pad[1]), bias, float(negative_slope), float(scale))
 
 
+def blur_pads(n_taps: int, kernel_size: int, up: bool):
+    """(pad0, pad1) of the Blur behind a stride-2 transposed conv (``up``; stylegan2/model.py:202-208) or in front of a stride-2
+    conv (:212-216): the one statement of the rule, for ConvLayer and for both resampling branches of the modulated conv."""
+    factor = 2
+    if up:
+        p = (n_taps - factor) - (kernel_size - 1)
+        return (p + 1) // 2 + factor - 1, p // 2 + 1
+    p = (n_taps - factor) + (kernel_size - 1)
+    return (p + 1) // 2, p // 2
+
+
 def _geometry(in_hw, fir, up: int, down: int, pad2):
     """(pad4, out_hw, g_pad4) of ``upfirdn2d(x, fir, up, down, pad=pad2)`` (upfirdn2d.py:95-114)."""
     kh, kw = fir.shape

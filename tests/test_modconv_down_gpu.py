@@ -290,7 +290,7 @@ def test_frozen_weight_and_frozen_input(case, monkeypatch):
     def blurred_saved(y):
         """Saved tensors of the conv node of the blurred tensor's shape [B, Cin, H + 1, H + 1]."""
         fn = y.grad_fn
-        assert type(fn).__name__ == "_ModConvDownBackward", type(fn).__name__
+        assert type(fn).__name__ == "_ModConvBackward", type(fn).__name__
         return [t for t in fn.saved_tensors if t.dim() == 4 and tuple(t.shape) == (B, ci, H + 1, H + 1)]
 
     # everything trainable: the blurred tensor is kept for the weight gradient

@@ -2,7 +2,7 @@
 """Extraction accuracy (and FID) of a trained IDEAS checkpoint per jitter width: random bits -> containers -> 8-bit images -> bits.
 
     python evaluate.py [--sigma 1] [--delta 0 0.25 0.5] [--n_sample 50000] [--batch 32] [--container u8] [--seed 0]
-        [--attack SPEC [SPEC ...]] [--inception inception_<name>.pkl --inception_weights pt_inception-2015-12-05-6726825d.pth] CHECKPOINT
+        [--attack SPEC [SPEC ...]] [--ecc RATE] [--inception inception_<name>.pkl --inception_weights pt_inception-2015-12-05-6726825d.pth] CHECKPOINT
 
 Prints one line per delta, ``sigma=1 delta=25% ACC: 0.9999 FID: 15.56``.  The FID is printed only when both inception arguments are
 given: ``--inception`` is the pickle calc_inception.py wrote for the dataset, ``--inception_weights`` pytorch-fid's FID Inception state
@@ -12,6 +12,10 @@ dict (not shipped); it is computed as fid.py does, on the containers the receive
 (quality 1..100), ``noise:S`` (Gaussian, S in 8-bit levels), ``sp:P`` (salt and pepper, fraction P), ``gain:G``, ``offset:D``, or a
 chain such as ``noise:3+jpeg:75``.  One line per attack and delta, ``sigma=1 delta=25% attack=jpeg:75 ACC: 0.9871``; the generator
 is re-seeded for every line, so every attack sees the same messages and textures.
+
+``--ecc RATE`` (1/2, 2/3 or 3/4) makes every container carry one codeword of ``ideas_amd.ecc``: ACC then counts the channel's errors
+on the coded bits, and each line ends in `` ECC=1/2 INFO_ACC: 0.9999 FER: 0.0003``, the accuracy of the decoded information bits and
+the fraction of images with any wrong one.
 """
 import argparse
 import pickle
@@ -29,6 +33,7 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--attack", type=str, nargs="+", default=None, metavar="SPEC",
                         help="channel attacks on the 8-bit container: none, jpeg:Q, noise:S, sp:P, gain:G, offset:D, chained with +")
+    parser.add_argument("--ecc", type=str, default=None, metavar="RATE", help="forward error correction of rate 1/2, 2/3 or 3/4")
     parser.add_argument("--inception", type=str, default=None, help="dataset statistics written by calc_inception.py")
     parser.add_argument("--inception_weights", type=str, default=None, help="pt_inception-2015-12-05-6726825d.pth (pytorch-fid)")
     parser.add_argument("ckpt", metavar="CHECKPOINT", nargs="?")
@@ -46,6 +51,9 @@ def main(argv=None):
         parser.error(str(e))
     if opt.attack is not None and opt.container != "u8":
         parser.error("--attack acts on the 8-bit container: it needs --container u8")
+    from ideas_amd import ecc
+    if opt.ecc is not None and opt.ecc not in ecc.RATES:
+        parser.error(f"--ecc: unknown rate {opt.ecc!r} (known: {', '.join(ecc.RATES)})")
 
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs a GPU (ideas_amd has no CPU path)")
@@ -57,6 +65,12 @@ def main(argv=None):
     cap = stego.capacity_bits(args, opt.sigma)
     if cap % 8:
         raise SystemExit(f"evaluate.py: the capacity of an image ({cap} bits) is not a whole number of bytes (needs image_size >= 64)")
+    code = None
+    if opt.ecc is not None:
+        try:
+            code = ecc.Code(cap, opt.ecc)
+        except ValueError as e:
+            raise SystemExit(f"evaluate.py: {e}")
     inception, embeds = None, None
     if opt.inception is not None:
         from ideas_amd.inception import InceptionV3
@@ -67,12 +81,14 @@ def main(argv=None):
         for delta in opt.delta:
             gen = torch.Generator(device=device).manual_seed(opt.seed)
             res = stego.evaluate(models, args, opt.sigma, delta, opt.n_sample, opt.batch, gen, container=opt.container,
-                                 inception=inception, attack=attack)
+                                 inception=inception, attack=attack, code=code)
             line = f"sigma={opt.sigma} delta={delta * 100:g}%" + ("" if attack is None else f" attack={attack.name}")
             line += f" ACC: {res['acc']:.4f}"
             if inception is not None:
                 stats = res["stats"]
                 line += f" FID: {calc_fid(stats.mean(), stats.cov(), embeds['mean'], embeds['cov']):.2f}"
+            if code is not None:
+                line += f" ECC={code.rate} INFO_ACC: {res['info_acc']:.4f} FER: {res['n_row_err'] / opt.n_sample:.4f}"
             print(line)
 
 

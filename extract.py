@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Get a hidden file back from container images (the receiver of IDEAS: 8-bit images -> E -> Ex -> bits -> payload).
 
-    python extract.py --ckpt CHECKPOINT [--sigma 1] --out FILE [--dump_bits F.npy] [--batch 32] IMAGES...
+    python extract.py --ckpt CHECKPOINT [--sigma 1] --out FILE [--dump_bits F.npy] [--batch 32] [--ecc RATE] IMAGES...
 
 ``IMAGES`` are the files ``hide.py`` wrote, in order.  Exit status 0 and the payload in ``FILE`` when the length and the CRC32 of the
 frame hold; status 1 with a one-line message and no payload file when they do not.  ``--dump_bits`` saves the extracted packed bits
 (uint8 [n_images, capacity / 8]) whatever the check says.
+
+``--ecc RATE`` as given to ``hide.py``: the rows are decoded from soft values of the extractor's output (``ideas_amd.ecc``) before the
+frame is checked, and ``--dump_bits`` saves the decoded information rows (uint8 [n_images, info bytes per image]).
 """
 import argparse
 import sys
@@ -21,8 +24,12 @@ def main(argv=None):
     parser.add_argument("--out", type=str, required=True, help="where the payload is written")
     parser.add_argument("--dump_bits", type=str, default=None, metavar="F.npy", help="also save the extracted packed bits")
     parser.add_argument("--batch", type=int, default=32)
+    parser.add_argument("--ecc", type=str, default=None, metavar="RATE", help="the forward error correction given to hide.py")
     parser.add_argument("images", metavar="IMAGES", nargs="+")
     opt = parser.parse_args(argv)
+    from ideas_amd import ecc
+    if opt.ecc is not None and opt.ecc not in ecc.RATES:
+        parser.error(f"--ecc: unknown rate {opt.ecc!r} (known: {', '.join(ecc.RATES)})")
 
     if not torch.cuda.is_available():
         raise SystemExit("extract.py needs a GPU (ideas_amd has no CPU path)")
@@ -34,6 +41,12 @@ def main(argv=None):
     cap = stego.capacity_bits(args, opt.sigma)
     if cap % 8:
         raise SystemExit(f"extract.py: the capacity of an image ({cap} bits) is not a whole number of bytes (needs image_size >= 64)")
+    code = None
+    if opt.ecc is not None:
+        try:
+            code = ecc.Code(cap, opt.ecc)
+        except ValueError as e:
+            raise SystemExit(f"extract.py: {e}")
     size = int(args.image_size)
     rows = []
     for i0 in range(0, len(opt.images), opt.batch):
@@ -44,7 +57,10 @@ def main(argv=None):
             if arr.shape != (size, size, 3):
                 raise SystemExit(f"extract.py: {path} is {arr.shape[1]}x{arr.shape[0]}, the checkpoint's images are {size}x{size}")
             batch.append(torch.from_numpy(arr.copy()))
-        bits, _ = stego.extract(models, args, torch.stack(batch).to(device), opt.sigma)
+        if code is None:
+            bits, _ = stego.extract(models, args, torch.stack(batch).to(device), opt.sigma)
+        else:
+            bits, _, _ = stego.extract_coded(models, args, torch.stack(batch).to(device), opt.sigma, code)
         rows.append(bits.cpu())
     rows = torch.cat(rows, 0)
     if opt.dump_bits:

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Hide a file in synthesised images (the sender of IDEAS: payload bits -> secret tensor -> Gstru -> G -> 8-bit PNGs).
 
-    python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32]
+    python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32] [--ecc RATE]
 
 The payload is framed (4-byte length, CRC32, payload, random padding: ``ideas_amd.stego.frame``) into whole images of
 ``N * (image_size / 16)^2 * sigma`` bits each and written as ``DIR/000000.png``, ``DIR/000001.png``, ...  ``extract.py`` with the same
 checkpoint and ``--sigma`` reads them back.  The same ``--seed`` gives the same files.
+
+``--ecc RATE`` (1/2, 2/3 or 3/4) protects the frame with forward error correction (``ideas_amd.ecc``): every image then carries one
+codeword of a punctured convolutional code, fewer payload bytes, and ``extract.py --ecc RATE`` corrects the receiver's wrong bits.
 """
 import argparse
 import os
@@ -22,7 +25,11 @@ def main(argv=None):
     parser.add_argument("--delta", type=float, default=0.5, help="jitter half-width as a fraction of a bin")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--batch", type=int, default=32)
+    parser.add_argument("--ecc", type=str, default=None, metavar="RATE", help="forward error correction of rate 1/2, 2/3 or 3/4")
     opt = parser.parse_args(argv)
+    from ideas_amd import ecc
+    if opt.ecc is not None and opt.ecc not in ecc.RATES:
+        parser.error(f"--ecc: unknown rate {opt.ecc!r} (known: {', '.join(ecc.RATES)})")
 
     if not torch.cuda.is_available():
         raise SystemExit("hide.py needs a GPU (ideas_amd has no CPU path)")
@@ -37,10 +44,19 @@ def main(argv=None):
         raise SystemExit(f"hide.py: the capacity of an image ({cap} bits) is not a whole number of bytes (needs image_size >= 64)")
     with open(opt.payload, "rb") as f:
         payload = f.read()
-    rows = stego.frame(payload, cap // 8, torch.Generator().manual_seed(opt.seed))
+    if opt.ecc is None:
+        rows = stego.frame(payload, cap // 8, torch.Generator().manual_seed(opt.seed))
+        room = f"{cap} bits ({cap // 8} bytes)"
+    else:
+        try:
+            code = ecc.Code(cap, opt.ecc)
+        except ValueError as e:
+            raise SystemExit(f"hide.py: {e}")
+        rows = stego.frame_coded(payload, code, torch.Generator().manual_seed(opt.seed), device)
+        room = f"{cap} bits, ECC {opt.ecc}: {code.k_bytes} info bytes"
     gen = torch.Generator(device=device).manual_seed(opt.seed)
     os.makedirs(opt.out, exist_ok=True)
-    print(f"capacity per image: {cap} bits ({cap // 8} bytes); payload {len(payload)} bytes -> {rows.shape[0]} image(s)")
+    print(f"capacity per image: {room}; payload {len(payload)} bytes -> {rows.shape[0]} image(s)")
     for i0 in range(0, rows.shape[0], opt.batch):
         bits = rows[i0:i0 + opt.batch].to(device)
         images, _ = stego.hide(models, args, bits, opt.sigma, opt.delta, generator=gen)

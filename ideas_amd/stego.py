@@ -7,6 +7,9 @@ the extraction accuracy (and FID) per jitter width -- the sender / receiver bloc
 Messages are PACKED bits (``ideas_amd.op.stego``): uint8 ``[B, capacity_bits / 8]``.  The networks are the EMA copies of a checkpoint
 (``load_models``) or of a trainer (``models_of``).  ``frame`` / ``unframe`` put a byte payload into whole images: a 4-byte big-endian
 length, the CRC32 of the payload, the payload, random padding.  Everything on the device runs under ``no_grad``.
+
+With a ``Code`` of ``ideas_amd.ecc`` the framed rows are the INFORMATION bits of one codeword per image (``frame_coded``), the receiver
+decodes them from soft values of ``hat_Z`` (``extract_coded``), and ``evaluate(code=...)`` counts what survives the decoder.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, checkpoint, data, fid
+from . import _lib, checkpoint, data, ecc, fid
 from .op import stego as S
 
 NETS = ("E", "G", "Gstru", "Ex")
@@ -105,6 +108,25 @@ def extract(models, args, images: torch.Tensor, sigma: int, ref_bits: Optional[t
     return out[0], hat_Z, out[1]
 
 
+def _decode_coded(hat_Z: torch.Tensor, sigma: int, code: "ecc.Code"):
+    return ecc.decode(code, ecc.soft_bits(hat_Z.reshape(hat_Z.shape[0], -1), sigma))
+
+
+@torch.no_grad()
+def extract_coded(models, args, images: torch.Tensor, sigma: int, code: "ecc.Code"):
+    """``extract`` for containers that carry codewords of ``code`` (``frame_coded``): ``(info_rows, hat_Z, metric)``, the decoded
+    information rows uint8 [B, code.k_bytes], the extractor's output, and the decoder's final metric int32 [B]."""
+    _lib.require_cuda(images)
+    if code.n_bits != capacity_bits(args, sigma):
+        raise ValueError(f"extract_coded: the code is planned for {code.n_bits} message bits, an image carries {capacity_bits(args, sigma)}")
+    if images.dtype == torch.uint8:
+        images = data.u8_to_f32(images.contiguous())
+    hat_S, _ = models["E"](images)
+    hat_Z = models["Ex"](hat_S)
+    info, metric = _decode_coded(hat_Z, sigma, code)
+    return info, hat_Z, metric
+
+
 # ---------------------------------------------------------------------------------------------------------------- payload framing
 def frame(payload: bytes, capacity_bytes: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """``payload`` -> uint8 [n_img, capacity_bytes] (CPU): length (4 bytes, big-endian), ``zlib.crc32(payload)`` (4 bytes, big-endian),
@@ -120,6 +142,13 @@ def frame(payload: bytes, capacity_bytes: int, generator: Optional[torch.Generat
     rows = torch.randint(0, 256, (n_img * capacity_bytes,), generator=generator, dtype=torch.uint8)
     rows[:len(body)] = torch.frombuffer(bytearray(body), dtype=torch.uint8)
     return rows.view(n_img, capacity_bytes)
+
+
+def frame_coded(payload: bytes, code: "ecc.Code", generator: Optional[torch.Generator] = None, device="cuda") -> torch.Tensor:
+    """``frame(payload, code.k_bytes, generator)`` encoded: packed message rows uint8 [n_img, ceil(code.n_bits / 8)] on ``device``, one
+    codeword per image; the message bits the codewords do not reach are drawn from ``generator`` after the frame's padding."""
+    rows = frame(payload, code.k_bytes, generator).to(device)
+    return ecc.encode(code, rows, fill=random_bits(rows.shape[0], code.n_bits, generator, device))
 
 
 def unframe(rows) -> bytes:
@@ -144,7 +173,7 @@ def unframe(rows) -> bytes:
 # ---------------------------------------------------------------------------------------------------------------------- evaluation
 @torch.no_grad()
 def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, generator: Optional[torch.Generator] = None,
-             container: str = "u8", inception=None, attack=None) -> dict:
+             container: str = "u8", inception=None, attack=None, code: Optional["ecc.Code"] = None) -> dict:
     """Extraction accuracy over ``n_sample`` containers carrying random bits: ``n_sample // batch`` full batches and the remainder (a
     zero remainder is skipped).  Per batch, in this order of draws from ``generator``: the bits, the jitter, the texture codes.
     ``container``: ``"u8"`` sends every image through 8 bits (``quantize_image``), ``"float"`` hands the generator's output to the
@@ -154,8 +183,13 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
     ``attack(quantize_image(images)[0], generator)[1]``, the attack's draws come after the texture codes of the same batch, and the
     feature statistics are taken on what the receiver sees.  One host synchronisation, at the end.
 
+    With ``code`` (``ideas_amd.ecc.Code(capacity_bits(args, sigma), rate)``) every container carries one codeword: per batch the draws
+    are ``code.k_bytes`` of information per image, the fill bits, then the jitter and the texture codes as above.  ``acc`` / ``n_err``
+    then count the channel's errors against the CODED bits, and the soft-decision decoder runs on ``hat_Z``.
+
     Returns ``acc`` (1 - n_err / n_bits), ``n_bits``, ``n_err``, ``l1`` (mean |hat_Z - Z|), ``stats`` (``fid.FeatureStats`` or None)
-    and ``attack`` (the attack's name or None)."""
+    and ``attack`` (the attack's name or None); with ``code`` also ``info_acc`` (1 - n_info_err / n_info_bits), ``n_info_bits``,
+    ``n_info_err``, ``n_row_err`` (images with any wrong information bit) and ``rate``."""
     if container not in ("u8", "float"):
         raise ValueError(f"evaluate: container must be 'u8' or 'float', got {container!r}")
     if attack is not None and container != "u8":
@@ -164,14 +198,22 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
         raise ValueError("evaluate: n_sample and batch must be positive")
     device = next(models["G"].parameters()).device
     cap = capacity_bits(args, sigma)
+    if code is not None and code.n_bits != cap:
+        raise ValueError(f"evaluate: the code is planned for {code.n_bits} message bits, an image carries {cap}")
     err = torch.zeros((), device=device, dtype=torch.int64)
     l1 = torch.zeros((), device=device, dtype=torch.float64)
+    info_err = torch.zeros((), device=device, dtype=torch.int64)
+    row_err = torch.zeros((), device=device, dtype=torch.int64)
 
     def batches():
         for b in [batch] * (n_sample // batch) + [n_sample % batch]:
             if b == 0:
                 continue
-            bits = random_bits(b, cap, generator, device)
+            if code is None:
+                bits = random_bits(b, cap, generator, device)
+            else:
+                info = random_bits(b, code.k_bits, generator, device)
+                bits = ecc.encode(code, info, generator=generator)
             images, Z = hide(models, args, bits, sigma, delta, generator=generator)
             if attack is not None:
                 received = attack(S.quantize_image(images, dequantize=False)[0], generator)[1]
@@ -180,6 +222,10 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
             _, hat_Z, n_err = extract(models, args, received, sigma, ref_bits=bits)
             err.add_(n_err.sum())
             l1.add_((hat_Z.float() - Z).abs().sum(dtype=torch.float64))
+            if code is not None:
+                wrong = S.unpack_bits(_decode_coded(hat_Z, sigma, code)[0] ^ info, code.k_bits).sum(1)     # per image, exact in f32
+                info_err.add_(wrong.sum(dtype=torch.int64))
+                row_err.add_((wrong > 0).sum())
             yield received
 
     stats = None
@@ -189,6 +235,14 @@ def evaluate(models, args, sigma: int, delta: float, n_sample: int, batch: int, 
         for _ in batches():
             pass
     n_bits = n_sample * cap
-    n_err = int(err.item())
-    return {"acc": 1.0 - n_err / n_bits, "n_bits": n_bits, "n_err": n_err, "l1": float(l1.item()) / (n_sample * cap // int(sigma)),
-            "stats": stats, "attack": None if attack is None else attack.name}
+    if code is None:
+        n_err, l1_sum = int(err.item()), float(l1.item())
+    else:                                                     # still one synchronisation: the four sums cross together
+        n_err, l1_sum, n_info_err, n_row_err = torch.stack((err.double(), l1, info_err.double(), row_err.double())).tolist()
+        n_err, n_info_err, n_row_err = int(n_err), int(n_info_err), int(n_row_err)
+    res = {"acc": 1.0 - n_err / n_bits, "n_bits": n_bits, "n_err": n_err, "l1": l1_sum / (n_sample * cap // int(sigma)),
+           "stats": stats, "attack": None if attack is None else attack.name}
+    if code is not None:
+        n_info = n_sample * code.k_bits
+        res.update(info_acc=1.0 - n_info_err / n_info, n_info_bits=n_info, n_info_err=n_info_err, n_row_err=n_row_err, rate=code.rate)
+    return res

@@ -683,6 +683,46 @@ int ideas_pixel_attack(void* out_u8, float* y, const void* x_u8, const float* no
                        float gain, float offset, float sigma, float sp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Payload coding, csrc/ecc.hip: forward error correction between stego.frame and the secret tensor.  Every image is ONE
+ * zero-terminated codeword of a punctured convolutional code, spread over the image's n message bits by an interleaver, and decoded
+ * from soft values read off the extractor's output.  The definitions (DESIGN.md "Payload coding"; tests/ecc_ref.py in numpy):
+ *   Mother code    r_t = (u_t << 6) | (r_{t-1} >> 1), r_{-1} = 0;  c0 = parity(r_t & 0171), c1 = parity(r_t & 0133) (octal).  The state
+ *                  after step t is r_t >> 1: the last six inputs, newest in bit 5.  Input 1,0,0,0,0,0,0 gives 11 10 11 11 00 01 11.
+ *   Termination    k information bits (k % 8 == 0) and 6 zero bits: T = k + 6 steps, the path ends in state 0.  T <= 2^20.
+ *   Puncturing     periodic in t; rate 1/2: c0 1, c1 1;  2/3: c0 1 1, c1 1 0;  3/4: c0 1 1 0, c1 1 0 1.  The kept outputs are
+ *                  numbered i = 0 .. m(T) - 1 in order of t, c0 before c1.  m(T) <= n.
+ *   Interleaver    coded position i (0 <= i < n) lives at message bit (i * P) mod n, gcd(P, n) = 1; Pinv is P's inverse mod n.
+ *                  Positions i >= m(T) carry fill bits, which the decoder ignores.  Packed rows as in the steganography codec: most significant
+ *                  bit first, pad bits of the last byte zero.
+ *   Soft value     of message bit j = element l = j / sigma, bit i = j % sigma (most significant first) of z [B][L]:
+ *                  c = min(max(z, -1), 1) (a NaN counts as -1); centres c_v = step * (v + 0.5) - 1, step = 2 / 2^sigma;
+ *                  d0 / d1 = min (c - c_v)^2 over the v whose bit is 0 / 1;  q = clamp(rint((d0 - d1) / step^2 * gain), -127, 127)
+ *                  as int8, positive favours 1.  Every step one f32 operation in that order, no contraction, round-half-even.
+ *   Decoder        int32 path metrics, state 0 starts at 0 and the others at -(1 << 30).  The branch metric of a transition is the sum
+ *                  over the kept outputs of the step of (c ? +q : -q); it is maximised.  The predecessors of state s' are
+ *                  p_b = ((s' & 31) << 1) | b; ON EQUAL METRICS b = 0 WINS (b = 1 only if strictly greater); the survivor bit is b.
+ *                  Traceback from state 0; u_t is bit 5 of the state after step t.  No metric normalisation (T <= 2^20).
+ *
+ *   ideas_ecc_encode   info: packed rows [B][k / 8];  fill: packed rows [B][ceil(n / 8)] or NULL (fill bits 0);  coded: packed rows
+ *                      [B][ceil(n / 8)].  A thread owns output bytes and recomputes the parity of the 7-bit window behind each bit.
+ *   ideas_ecc_soft     z [B][L] f32 or bf16 (widened exactly) -> soft int8 [B][L * sigma];  gain positive and finite.
+ *   ideas_ecc_viterbi  soft int8 [B][n] -> info packed rows [B][k / 8] (whole bytes; nothing else is written) and, if metric is not
+ *                      NULL, metric int [B]: the final metric of state 0.  One wave per image, lane = state; the 64 decisions of a
+ *                      step are one __ballot word.  The survivors (8 T bytes an image) live in LDS while 8 T <= 32768; a non-NULL
+ *                      workspace (uint64 [B][T]) ALWAYS selects the global route, a NULL one above that size is IDEAS_E_UNSUPPORTED.
+ *                      Both routes give the same bits.
+ * IDEAS_E_NULL: coded, info, soft or z is NULL.  IDEAS_E_SHAPE: B, n, k or L <= 0, k % 8 != 0, k + 6 > 2^20, m(k + 6) > n, P outside
+ * [1, n) or gcd(P, n) != 1, P * Pinv mod n != 1.  IDEAS_E_UNSUPPORTED: an unknown rate, sigma outside 1..8, a dtype other than
+ * f32 / bf16, a gain that is not positive and finite, survivors above the LDS size without a workspace.  Every check comes before
+ * any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#define IDEAS_ECC_RATE_1_2 0
+#define IDEAS_ECC_RATE_2_3 1
+#define IDEAS_ECC_RATE_3_4 2
+int ideas_ecc_encode(void* coded, const void* info, const void* fill, int B, int n, int k, int rate, int P, int Pinv, void* stream);
+int ideas_ecc_soft(void* soft, const void* z, int B, int L, int sigma, float gain, int dtype, void* stream);
+int ideas_ecc_viterbi(void* info, int* metric, const void* soft, void* workspace, int B, int n, int k, int rate, int P, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EqualLinear (stylegan2/model.py:131-160:  F.linear(input, weight * scale, bias * lr_mul)) for MANY layers sharing one input, one
  * launch per direction.  Replaces the ATen / vendor-GEMM calls behind F.linear on this path: every linear layer of IDEAS is skinny
  * (M = batch <= a few hundred rows, K = 32 .. 8192, N = 1 .. 512), and the generator applies sixteen of them (the modulation layers

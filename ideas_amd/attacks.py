@@ -1,5 +1,5 @@
 """The channel between sender and receiver as a value: ``parse("noise:3+jpeg:75")`` is a callable ``attack(u8, generator) -> (u8, y)``
-on the uint8 ``[B, H, W, C]`` container bytes, built from the kernels of ``ideas_amd.op.attack``.
+on the uint8 ``[B, H, W, C]`` container bytes, built from the kernels of ``ideas_amd.op.attack`` and ``ideas_amd.op.resample``.
 
     none          the lossless 8-bit file: the input and ``data.u8_to_f32`` of it
     jpeg:Q        a JPEG file of quality Q (integer, 1..100; 4:4:4)
@@ -7,6 +7,10 @@ on the uint8 ``[B, H, W, C]`` container bytes, built from the kernels of ``ideas
     sp:P          salt and pepper: a fraction P in [0, 1] of the pixels, half black, half white
     gain:G        intensity: contrast G about mid-grey
     offset:D      intensity: D 8-bit levels brighter
+    scale:F       rescaling, 0.25 <= F <= 4: Pillow's 8-bit bilinear resize to (max(1, floor(H F + 0.5)), max(1, floor(W F + 0.5))) --
+                  the 8-bit image the channel stores -- and back to (H, W)
+    gblur:S       Gaussian filtering of standard deviation S pixels, 0 < S <= 4 (ceil(3 S) taps either side, at most 25 in all)
+    median:K      median filtering over K x K pixels, K = 3 or 5, edges replicated
 
 Stages chain with ``+`` and run left to right, each on the bytes the one before it wrote; the chain returns the last stage's ``y``.
 ``attack.name`` is the spec in canonical spelling: ``parse(a.name).name == a.name``.  A bad spec raises ``ValueError`` naming the stage.
@@ -20,6 +24,7 @@ import torch
 
 from . import data
 from .op import attack as A
+from .op import resample as S
 
 Stage = Callable[[torch.Tensor, Optional[torch.Generator]], Tuple[torch.Tensor, torch.Tensor]]
 
@@ -41,8 +46,9 @@ def _stage(stage: str) -> Tuple[str, Optional[Stage]]:
         if sep:
             raise ValueError(f"attack stage {stage!r}: 'none' takes no argument")
         return "none", None
-    if kind not in ("jpeg", "noise", "sp", "gain", "offset"):
-        raise ValueError(f"attack stage {stage!r}: unknown attack {kind!r} (none, jpeg:Q, noise:S, sp:P, gain:G, offset:D)")
+    if kind not in ("jpeg", "noise", "sp", "gain", "offset", "scale", "gblur", "median"):
+        raise ValueError(f"attack stage {stage!r}: unknown attack {kind!r} (none, jpeg:Q, noise:S, sp:P, gain:G, offset:D, scale:F, "
+                         "gblur:S, median:K)")
     if not sep or not arg:
         raise ValueError(f"attack stage {stage!r}: {kind!r} needs an argument, as in '{kind}:VALUE'")
     v = _number(stage, arg)
@@ -61,7 +67,27 @@ def _stage(stage: str) -> Tuple[str, Optional[Stage]]:
         return f"sp:{v:g}", lambda u8, gen: A.pixel_attack(u8, sp=v, generator=gen)
     if kind == "gain":
         return f"gain:{v:g}", lambda u8, gen: A.pixel_attack(u8, gain=v)
+    if kind == "scale":
+        if not 0.25 <= v <= 4:
+            raise ValueError(f"attack stage {stage!r}: the scale factor must lie in [0.25, 4]")
+        return f"scale:{v:g}", lambda u8, gen: _rescale(u8, v)
+    if kind == "gblur":
+        if not 0 < v <= 4:
+            raise ValueError(f"attack stage {stage!r}: the Gaussian's sigma must lie in (0, 4]")
+        return f"gblur:{v:g}", lambda u8, gen: S.gaussian_blur_u8(u8, v)
+    if kind == "median":
+        if v not in (3, 5):
+            raise ValueError(f"attack stage {stage!r}: the median window must be 3 or 5")
+        k = int(v)
+        return f"median:{k}", lambda u8, gen: S.median_u8(u8, k)
     return f"offset:{v:g}", lambda u8, gen: A.pixel_attack(u8, offset=v)
+
+
+def _rescale(u8: torch.Tensor, factor: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """To ``factor`` times the size and back, both ways as Pillow's bilinear resize; the image in between is 8-bit.  Two launches."""
+    h, w = int(u8.shape[1]), int(u8.shape[2])
+    small = (max(1, math.floor(h * factor + 0.5)), max(1, math.floor(w * factor + 0.5)))
+    return S.resize_u8(S.resize_u8(u8, small)[0], (h, w))
 
 
 class Attack:
@@ -84,7 +110,8 @@ class Attack:
 
 
 def parse(spec: str) -> Attack:
-    """``"none"``, ``"jpeg:75"``, ``"noise:5"``, ``"sp:0.02"``, ``"gain:0.8"``, ``"offset:20"`` or a ``+`` chain of them."""
+    """``"none"``, ``"jpeg:75"``, ``"noise:5"``, ``"sp:0.02"``, ``"gain:0.8"``, ``"offset:20"``, ``"scale:0.5"``, ``"gblur:1"``,
+    ``"median:3"`` or a ``+`` chain of them."""
     if not isinstance(spec, str) or not spec.strip():
         raise ValueError(f"attack spec {spec!r}: expected a string such as 'jpeg:75' or 'noise:3+jpeg:75'")
     names, stages = [], []

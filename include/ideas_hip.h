@@ -683,6 +683,47 @@ int ideas_pixel_attack(void* out_u8, float* y, const void* x_u8, const float* no
                        float gain, float offset, float sigma, float sp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spatial channel attacks on the 8-bit container, csrc/attack_spatial.hip: rescaling, Gaussian filtering and median filtering, what
+ * a messenger or an image host does to a picture before it re-encodes it.  Integer arithmetic throughout: every result is defined
+ * to the byte (tests/spatial_ref.py restates it in numpy; the resize is Pillow's Image.resize(size, Image.BILINEAR) on 8-bit
+ * images and the median Pillow's ImageFilter.MedianFilter, byte for byte).  x_u8 is uint8 [B][H][W][C], C = 1 or 3; out_u8 must not
+ * overlap it; y (optional, float, the shape of out_u8) = (out_u8 / 255 - 0.5) / 0.5 as in the channel attacks above.
+ *
+ *   ideas_resample_u8   out_u8 [B][H2][W2][C]: a separable weighted window per output index, given as TABLES (device arrays of
+ *                       int32): lo [n_out], the first input index of output i, and kk [n_out][ksize], kk[i][j] the coefficient of
+ *                       input lo[i] + j in units of 2^-22, zero-padded to ksize (1 .. IDEAS_RESAMPLE_KMAX).  The model:
+ *     1. Horizontal pass, on every input row, with (h_lo, h_kk, h_ksize), n_in = W, n_out = W2:
+ *            s = 2^21 + sum_j kk[i][j] * p[clamp(lo[i] + j, 0, n_in - 1)]     in 32-bit integers
+ *            byte = clamp(s >> 22, 0, 255)                                     (arithmetic shift of the signed sum)
+ *        The result is ROUNDED TO BYTES: the vertical pass sees an 8-bit image [B][H][W2][C].
+ *     2. Vertical pass on those bytes with (v_lo, v_kk, v_ksize), n_in = H, n_out = H2, the same two lines.
+ *     3. A direction whose two table pointers are both NULL is skipped (its sizes must be equal), as Pillow skips it.
+ *     The index is clamped before the load, so a padded tap with coefficient 0 -- or a malformed table -- reads inside the image;
+ *     the sum is taken in unsigned 32-bit arithmetic and wraps.  Tables of a proper filter have rows that sum to 2^22 within
+ *     ksize / 2 (each coefficient is rounded on its own), so a constant image stays constant.
+ *     One launch: a workgroup owns 32 x 64 output pixels, runs the horizontal pass for the input rows its windows reach into LDS
+ *     (up to 160 rows of 64 C bytes; 30 KiB at C = 3) and the vertical pass out of LDS.  A tile whose windows reach more rows than
+ *     that (none does for a Pillow or Gaussian table within ksize <= 32 and scales 1/4 .. 4; a hand-made table can) computes the
+ *     same sums straight from x_u8: the same bytes, no workspace, no second launch.  Four output bytes a thread: one 4-byte store and
+ *     one float4 of y when out_u8 is 4-byte aligned, y 16-byte aligned and W2 * C % 4 == 0; byte by byte otherwise.
+ *     IDEAS_E_NULL: x_u8 or out_u8 is NULL, or exactly one of a direction's two tables.  IDEAS_E_SHAPE: B, H, W, H2 or W2 <= 0, C
+ *     other than 1 or 3, a skipped direction with unequal sizes.  IDEAS_E_UNSUPPORTED: the ksize of a direction that is not skipped
+ *     lies outside 1 .. IDEAS_RESAMPLE_KMAX (a skipped direction's ksize is ignored).
+ *
+ *   ideas_median_u8     out_u8 [B][H][W][C]: per channel the median of the K x K window around each pixel, the image extended by
+ *                       replicating its edge rows and columns; K = 3 or 5 (IDEAS_E_UNSUPPORTED otherwise).  One launch: a workgroup
+ *                       stages 16 x 64 pixels and their halo in LDS as bytes; a thread finds the medians of four consecutive bytes
+ *                       with min/max exchange networks in registers (9 values: the 19-exchange network; 25: forgetful selection,
+ *                       132 exchanges).  IDEAS_E_NULL: x_u8 or out_u8 is NULL.  IDEAS_E_SHAPE: B, H or W <= 0, C other than 1 or 3.
+ * Every check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#define IDEAS_RESAMPLE_KMAX 32
+int ideas_resample_u8(void* out_u8, void* y, const void* x_u8, int B, int C, int H, int W, int H2, int W2,
+                      const int32_t* h_lo, const int32_t* h_kk, int h_ksize,     /* [W2], [W2][h_ksize] */
+                      const int32_t* v_lo, const int32_t* v_kk, int v_ksize,     /* [H2], [H2][v_ksize] */
+                      void* stream);
+int ideas_median_u8(void* out_u8, void* y, const void* x_u8, int B, int C, int H, int W, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Payload coding, csrc/ecc.hip: forward error correction between stego.frame and the secret tensor.  Every image is ONE
  * zero-terminated codeword of a punctured convolutional code, spread over the image's n message bits by an interleaver, and decoded
  * from soft values read off the extractor's output.  The definitions (DESIGN.md "Payload coding"; tests/ecc_ref.py in numpy):

@@ -7,7 +7,11 @@ Device events around windows of ``--launches`` calls, warm-up, the variants alte
 per-call time.  The calls of a window rotate over ``--sets`` input tensors.  The kernel's time is also given as the bytes it must move,
 B*H*W*C*(1 + 1 + 4), over the measured HBM copy rate.  The results are compared at the timed size.  Needs a GPU.
 
-    python tools/bench_attack.py [--out profiles/attack_jpeg.txt] [--batch 32] [--size 256] [--quality 75] [--reps 20]
+The spatial attacks (``op.resize_u8`` to half size and back -- the two launches of ``scale:0.5`` --, ``op.gaussian_blur_u8`` and
+``op.median_u8``) are timed the same way at the same size, through their ops, and written to ``--spatial_out``.
+
+    python tools/bench_attack.py [--out profiles/attack_jpeg.txt] [--spatial_out profiles/attack_spatial.txt] [--batch 32] [--size 256]
+        [--quality 75] [--reps 20]
 """
 import argparse
 import os
@@ -55,9 +59,38 @@ def window_ms(fn, xs, launches):
     return a.elapsed_time(b) / launches
 
 
+def spatial(xs, args):
+    """Per-call times of the spatial attacks through their ops, and the bytes a call must move over the measured HBM copy rate."""
+    from ideas_amd.op import gaussian_blur_u8, median_u8, resize_u8
+    b, r = args.batch, args.size
+    n = b * 3 * r * r
+    half = (max(1, r // 2), max(1, r // 2))
+    variants = (("scale:0.5", lambda x: resize_u8(resize_u8(x, half)[0], (r, r)), 2, n * (1 + 0.25 * 5) + n * (0.25 + 5)),
+                ("gblur:1", lambda x: gaussian_blur_u8(x, 1.0), 1, n * 6), ("gblur:4", lambda x: gaussian_blur_u8(x, 4.0), 1, n * 6),
+                ("median:3", lambda x: median_u8(x, 3), 1, n * 6), ("median:5", lambda x: median_u8(x, 5), 1, n * 6))
+    for _ in range(args.warmup):
+        for _, fn, _, _ in variants:
+            window_ms(fn, xs, args.launches)
+    torch.cuda.synchronize()
+    ts = {name: [] for name, _, _, _ in variants}
+    for _ in range(args.reps):
+        for name, fn, _, _ in variants:
+            ts[name].append(window_ms(fn, xs, args.launches))
+    lines = ["spatial attacks on the container, (%d, %d, %d, 3) uint8 with the received image, through the ops (output allocation included); "
+             "per-call ms over windows of %d calls rotating over %d inputs, median of %d alternating windows [min .. max]; bytes = input, "
+             "output and received image of every launch" % (b, r, r, args.launches, args.sets, args.reps)]
+    for name, _, launches, moved in variants:
+        v = ts[name]
+        t = statistics.median(v)
+        lines.append("%-9s %8.4f  [%8.4f .. %8.4f]  %d launch(es), %.1f MB -> %.2f TB/s = %.0f %% of the measured HBM copy rate"
+                     % (name, t, min(v), max(v), launches, moved / 1e6, moved / (t * 1e-3) / 1e12, 100 * moved / (t * 1e-3) / HBM_MEASURED))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attack_jpeg.txt"))
+    ap.add_argument("--spatial_out", default=os.path.join(ROOT, "profiles", "attack_spatial.txt"))
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=75)
@@ -125,6 +158,11 @@ def main():
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("wrote", args.out)
+    lines = spatial(xs, args)
+    print("\n".join(lines), flush=True)
+    with open(args.spatial_out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", args.spatial_out)
 
 
 if __name__ == "__main__":

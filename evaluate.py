@@ -9,7 +9,8 @@ given: ``--inception`` is the pickle calc_inception.py wrote for the dataset, ``
 dict (not shipped); it is computed as fid.py does, on the containers the receiver sees.  ``--container float`` skips the 8-bit file.
 
 ``--attack`` sends the 8-bit containers through a channel before the receiver sees them (``ideas_amd.attacks``): ``none``, ``jpeg:Q``
-(quality 1..100), ``noise:S`` (Gaussian, S in 8-bit levels), ``sp:P`` (salt and pepper, fraction P), ``gain:G``, ``offset:D``,
+(quality 1..100; an f32 model at 4:4:4), ``jpegfile:Q`` (the JPEG file libjpeg / Pillow writes at quality Q, 4:2:0, exact to the byte;
+``jpegfile:Q:444`` without chroma subsampling), ``noise:S`` (Gaussian, S in 8-bit levels), ``sp:P`` (salt and pepper, fraction P), ``gain:G``, ``offset:D``,
 ``scale:F`` (Pillow's bilinear resize to F times the size and back, 0.25..4), ``gblur:S`` (Gaussian filter, sigma S pixels, up to 4),
 ``median:K`` (K x K median, K = 3 or 5), or a chain such as ``noise:3+jpeg:75`` or ``scale:0.5+jpeg:75``.  One line per attack and
 delta, ``sigma=1 delta=25% attack=jpeg:75 ACC: 0.9871``; the generator is re-seeded for every line, so every attack sees the same
@@ -34,7 +35,7 @@ def main(argv=None):
     parser.add_argument("--container", choices=("u8", "float"), default="u8")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--attack", type=str, nargs="+", default=None, metavar="SPEC",
-                        help="channel attacks on the 8-bit container: none, jpeg:Q, noise:S, sp:P, gain:G, offset:D, scale:F, gblur:S, "
+                        help="channel attacks on the 8-bit container: none, jpeg:Q, jpegfile:Q[:444], noise:S, sp:P, gain:G, offset:D, scale:F, gblur:S, "
                              "median:K, chained with +")
     parser.add_argument("--ecc", type=str, default=None, metavar="RATE", help="forward error correction of rate 1/2, 2/3 or 3/4")
     parser.add_argument("--inception", type=str, default=None, help="dataset statistics written by calc_inception.py")

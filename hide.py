@@ -2,6 +2,7 @@
 """Hide a file in synthesised images (the sender of IDEAS: payload bits -> secret tensor -> Gstru -> G -> 8-bit PNGs).
 
     python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32] [--ecc RATE]
+                   [--format png|jpeg] [--jpeg_quality 90] [--jpeg_subsampling 420|444]
 
 The payload is framed (4-byte length, CRC32, payload, random padding: ``ideas_amd.stego.frame``) into whole images of
 ``N * (image_size / 16)^2 * sigma`` bits each and written as ``DIR/000000.png``, ``DIR/000001.png``, ...  ``extract.py`` with the same
@@ -9,6 +10,11 @@ checkpoint and ``--sigma`` reads them back.  The same ``--seed`` gives the same 
 
 ``--ecc RATE`` (1/2, 2/3 or 3/4) protects the frame with forward error correction (``ideas_amd.ecc``): every image then carries one
 codeword of a punctured convolutional code, fewer payload bytes, and ``extract.py --ecc RATE`` corrects the receiver's wrong bits.
+
+``--format jpeg`` writes ``DIR/000000.jpg``, ... through Pillow with ``quality=--jpeg_quality`` and ``subsampling=2`` (4:2:0, the
+default) or ``0`` (``--jpeg_subsampling 444``), nothing else.  A JPEG file is a lossy channel: what ``extract.py`` reads out of it is
+``op.jpeg_file_roundtrip`` of the container's bytes, and ``evaluate.py --attack jpegfile:Q`` (``jpegfile:Q:444``) gives the accuracy
+to expect behind it; use ``--ecc``.
 """
 import argparse
 import os
@@ -20,13 +26,18 @@ def main(argv=None):
     parser = argparse.ArgumentParser(description="hide a payload file in images synthesised by a trained IDEAS checkpoint")
     parser.add_argument("--ckpt", type=str, required=True, help="checkpoint in the reference's format ({iter}.pt)")
     parser.add_argument("--payload", type=str, required=True, help="the file to hide")
-    parser.add_argument("--out", type=str, required=True, help="directory for the PNG containers")
+    parser.add_argument("--out", type=str, required=True, help="directory for the containers")
     parser.add_argument("--sigma", type=int, default=1, help="bits per element of the secret tensor (1..8)")
     parser.add_argument("--delta", type=float, default=0.5, help="jitter half-width as a fraction of a bin")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--batch", type=int, default=32)
     parser.add_argument("--ecc", type=str, default=None, metavar="RATE", help="forward error correction of rate 1/2, 2/3 or 3/4")
+    parser.add_argument("--format", choices=("png", "jpeg"), default="png", help="container files: lossless PNG or JPEG (a lossy channel)")
+    parser.add_argument("--jpeg_quality", type=int, default=90, metavar="Q", help="with --format jpeg: the quality, 1..100")
+    parser.add_argument("--jpeg_subsampling", choices=("420", "444"), default="420", help="with --format jpeg: the chroma subsampling")
     opt = parser.parse_args(argv)
+    if not 1 <= opt.jpeg_quality <= 100:
+        parser.error(f"--jpeg_quality: {opt.jpeg_quality} is outside 1..100")
     from ideas_amd import ecc
     if opt.ecc is not None and opt.ecc not in ecc.RATES:
         parser.error(f"--ecc: unknown rate {opt.ecc!r} (known: {', '.join(ecc.RATES)})")
@@ -62,7 +73,12 @@ def main(argv=None):
         images, _ = stego.hide(models, args, bits, opt.sigma, opt.delta, generator=gen)
         u8, _ = quantize_image(images, dequantize=False)
         for k, img in enumerate(u8.cpu().numpy()):
-            Image.fromarray(img).save(os.path.join(opt.out, f"{i0 + k:06d}.png"))
+            im = Image.fromarray(img[..., 0] if img.shape[2] == 1 else img)
+            if opt.format == "jpeg":
+                im.save(os.path.join(opt.out, f"{i0 + k:06d}.jpg"), "JPEG", quality=opt.jpeg_quality,
+                        subsampling=2 if opt.jpeg_subsampling == "420" else 0)
+            else:
+                im.save(os.path.join(opt.out, f"{i0 + k:06d}.png"))
     print(f"wrote {rows.shape[0]} image(s) to {opt.out}")
 
 

@@ -164,6 +164,8 @@ _PROTOS = {
     "ideas_pair_prepare": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)] + [C.c_int] * 7 + [_P]),
     "ideas_jpeg_roundtrip": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_pixel_attack": (C.c_int, [_P] * 5 + [C.c_int] * 4 + [C.c_float] * 4 + [_P]),
+    "ideas_jpeg_file_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "ideas_jpeg_file_roundtrip": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [_P]),
     "ideas_resample_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "ideas_median_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_ecc_encode": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),

@@ -3,6 +3,9 @@ on the uint8 ``[B, H, W, C]`` container bytes, built from the kernels of ``ideas
 
     none          the lossless 8-bit file: the input and ``data.u8_to_f32`` of it
     jpeg:Q        a JPEG file of quality Q (integer, 1..100; 4:4:4)
+    jpegfile:Q    the JPEG FILE libjpeg / Pillow writes at quality Q with its defaults, exact to the byte: integer DCT, 4:2:0 chroma,
+                  triangle upsampler (what ``Image.save(f, "JPEG", quality=Q)`` stores).  ``jpegfile:Q:444`` keeps 4:4:4 chroma
+                  (``subsampling=0``); ``jpegfile:Q:420`` is ``jpegfile:Q``
     noise:S       additive Gaussian noise of standard deviation S >= 0, in 8-bit levels
     sp:P          salt and pepper: a fraction P in [0, 1] of the pixels, half black, half white
     gain:G        intensity: contrast G about mid-grey
@@ -46,8 +49,10 @@ def _stage(stage: str) -> Tuple[str, Optional[Stage]]:
         if sep:
             raise ValueError(f"attack stage {stage!r}: 'none' takes no argument")
         return "none", None
+    if kind == "jpegfile":
+        return _jpegfile(stage, sep, arg)
     if kind not in ("jpeg", "noise", "sp", "gain", "offset", "scale", "gblur", "median"):
-        raise ValueError(f"attack stage {stage!r}: unknown attack {kind!r} (none, jpeg:Q, noise:S, sp:P, gain:G, offset:D, scale:F, "
+        raise ValueError(f"attack stage {stage!r}: unknown attack {kind!r} (none, jpeg:Q, jpegfile:Q[:444], noise:S, sp:P, gain:G, offset:D, scale:F, "
                          "gblur:S, median:K)")
     if not sep or not arg:
         raise ValueError(f"attack stage {stage!r}: {kind!r} needs an argument, as in '{kind}:VALUE'")
@@ -83,6 +88,20 @@ def _stage(stage: str) -> Tuple[str, Optional[Stage]]:
     return f"offset:{v:g}", lambda u8, gen: A.pixel_attack(u8, offset=v)
 
 
+def _jpegfile(stage: str, sep: str, arg: str) -> Tuple[str, Stage]:
+    """``jpegfile:Q[:420|:444]``."""
+    if not sep or not arg:
+        raise ValueError(f"attack stage {stage!r}: 'jpegfile' needs an argument, as in 'jpegfile:75' or 'jpegfile:75:444'")
+    text, colon, suffix = arg.partition(":")
+    v = _number(stage, text)
+    if v != int(v) or not 1 <= v <= 100:
+        raise ValueError(f"attack stage {stage!r}: the JPEG quality must be an integer in 1..100")
+    if colon and suffix not in ("420", "444"):
+        raise ValueError(f"attack stage {stage!r}: the chroma subsampling must be 420 or 444, as in 'jpegfile:75:444'")
+    q, sub = int(v), "4:4:4" if suffix == "444" else "4:2:0"
+    return f"jpegfile:{q}" + (":444" if suffix == "444" else ""), lambda u8, gen: A.jpeg_file_roundtrip(u8, q, sub)
+
+
 def _rescale(u8: torch.Tensor, factor: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """To ``factor`` times the size and back, both ways as Pillow's bilinear resize; the image in between is 8-bit.  Two launches."""
     h, w = int(u8.shape[1]), int(u8.shape[2])
@@ -110,7 +129,7 @@ class Attack:
 
 
 def parse(spec: str) -> Attack:
-    """``"none"``, ``"jpeg:75"``, ``"noise:5"``, ``"sp:0.02"``, ``"gain:0.8"``, ``"offset:20"``, ``"scale:0.5"``, ``"gblur:1"``,
+    """``"none"``, ``"jpeg:75"``, ``"jpegfile:75"``, ``"jpegfile:75:444"``, ``"noise:5"``, ``"sp:0.02"``, ``"gain:0.8"``, ``"offset:20"``, ``"scale:0.5"``, ``"gblur:1"``,
     ``"median:3"`` or a ``+`` chain of them."""
     if not isinstance(spec, str) or not spec.strip():
         raise ValueError(f"attack spec {spec!r}: expected a string such as 'jpeg:75' or 'noise:3+jpeg:75'")

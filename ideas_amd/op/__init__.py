@@ -20,12 +20,12 @@ from .lpips import lpips_layer, max_pool2x2
 from .pool import global_avg_pool, pool3x3
 from .stego import bits_to_tensor, pack_bits, quantize_image, tensor_to_bits, unpack_bits
 from .ppl import pair_prepare, path_endpoints
-from .attack import jpeg_roundtrip, pixel_attack
+from .attack import jpeg_file_roundtrip, jpeg_roundtrip, pixel_attack
 from .resample import gaussian_blur_u8, median_u8, resample_tables, resize_u8
 from .ecc import ecc_encode, ecc_soft, ecc_viterbi
 
 __all__ = ["FusedLeakyReLU", "fused_leaky_relu", "upfirdn2d", "conv2d", "conv2d_bias_act", "conv_transpose2d", "modulated_conv2d",
            "minibatch_stddev", "noise_bias_act", "affine_warp", "color_affine", "max_pool2x2", "lpips_layer",
            "pool3x3", "global_avg_pool", "bits_to_tensor", "tensor_to_bits", "quantize_image", "pack_bits", "unpack_bits",
-           "path_endpoints", "pair_prepare", "jpeg_roundtrip", "pixel_attack", "resize_u8", "gaussian_blur_u8", "median_u8", "resample_tables",
+           "path_endpoints", "pair_prepare", "jpeg_roundtrip", "jpeg_file_roundtrip", "pixel_attack", "resize_u8", "gaussian_blur_u8", "median_u8", "resample_tables",
            "ecc_encode", "ecc_soft", "ecc_viterbi"]

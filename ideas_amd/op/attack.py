@@ -1,10 +1,14 @@
-"""Channel attacks on the 8-bit container, on the HIP kernels of csrc/attack.hip: what a container suffers between sender and receiver.
+"""Channel attacks on the 8-bit container, on the HIP kernels of csrc/attack.hip and csrc/attack_jpeg.hip: what a container suffers
+between sender and receiver.
 
     jpeg_roundtrip(u8, quality)   a baseline-JPEG (4:4:4) encode and decode in one launch -- the model is stated step by step in
                                   include/ideas_hip.h and restated in numpy by tests/attacks_ref.py
+    jpeg_file_roundtrip(u8, quality, subsampling)
+                                  the JPEG FILE libjpeg / Pillow writes (integer DCT, 4:2:0 by default, triangle upsampler), exact
+                                  to the byte -- stated in include/ideas_hip.h, restated by tests/jpegfile_ref.py
     pixel_attack(u8, ...)         intensity (gain, offset), additive Gaussian noise (sigma) and salt and pepper (sp) in one launch
 
-Both take and return the uint8 ``[B, H, W, C]`` bytes of ``quantize_image`` (C = 1 or 3) together with ``y``, float32 ``[B, C, H, W]``
+All take and return the uint8 ``[B, H, W, C]`` bytes of ``quantize_image`` (C = 1 or 3) together with ``y``, float32 ``[B, C, H, W]``
 in channels_last memory: bitwise ``data.u8_to_f32`` of the returned bytes, the image a receiver decodes.  Device tensors only (no CPU
 branch); forward-only.
 """
@@ -44,6 +48,41 @@ def jpeg_roundtrip(u8: torch.Tensor, quality: int, return_coef: bool = False):
                                               _lib.stream_ptr())
         _lib.check(rc, "ideas_jpeg_roundtrip")
     return (out, y, coef) if return_coef else (out, y)
+
+
+_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2, 0: 0, 2: 2}
+
+
+def jpeg_file_roundtrip(u8: torch.Tensor, quality: int, subsampling="4:2:0", return_coef: bool = False):
+    """``u8`` through the JPEG FILE libjpeg / libjpeg-turbo writes at ``quality`` (1..100) with its defaults -- what Pillow's
+    ``Image.save(f, "JPEG", quality=quality, subsampling=...)`` writes and ``Image.open`` reads back, byte for byte: the integer DCT,
+    ``subsampling`` ``"4:2:0"`` (the default, also ``2``) or ``"4:4:4"`` (``0``), the triangle chroma upsampler -> ``(u8, y)``, or
+    ``(u8, y, coef_y, coef_c)`` with ``return_coef``: the quantised coefficients int16 ``[B, ceil(H/8), ceil(W/8), 64]`` and
+    ``[B, 2, cbh, cbw, 64]`` (Cb, Cr; the luma grid at 4:4:4, ``ceil(ceil(H/2)/8) x ceil(ceil(W/2)/8)`` at 4:2:0; ``None`` for
+    C = 1) at index ``8 u + v``.  One launch, two at 4:2:0 with C = 3 (the workspace is allocated here)."""
+    u8 = _bytes(u8, "jpeg_file_roundtrip")
+    if int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise RuntimeError(f"jpeg_file_roundtrip: quality must be an integer in 1..100, got {quality!r}")
+    sub = _SUBSAMPLING.get(subsampling) if isinstance(subsampling, (str, int)) and not isinstance(subsampling, bool) else None
+    if sub is None:
+        raise RuntimeError(f"jpeg_file_roundtrip: subsampling must be '4:4:4', '4:2:0', 0 or 2, got {subsampling!r}")
+    b, h, w, c = u8.shape
+    out, y = _outputs(u8)
+    coef_y = coef_c = None
+    if return_coef:
+        bh, bw = (h + 7) // 8, (w + 7) // 8
+        coef_y = torch.empty((b, bh, bw, 64), device=u8.device, dtype=torch.int16)
+        if c == 3:
+            cbh, cbw = (bh, bw) if sub == 0 else (((h + 1) // 2 + 7) // 8, ((w + 1) // 2 + 7) // 8)
+            coef_c = torch.empty((b, 2, cbh, cbw, 64), device=u8.device, dtype=torch.int16)
+    if u8.numel():
+        lib = _lib.load()
+        nbytes = int(lib.ideas_jpeg_file_workspace_bytes(b, c, h, w, sub))
+        work = torch.empty((nbytes,), device=u8.device, dtype=torch.uint8) if nbytes else None
+        rc = lib.ideas_jpeg_file_roundtrip(_lib.ptr(out), _lib.ptr(y), _lib.ptr(coef_y), _lib.ptr(coef_c), _lib.ptr(work), _lib.ptr(u8),
+                                           b, c, h, w, int(quality), sub, _lib.stream_ptr())
+        _lib.check(rc, "ideas_jpeg_file_roundtrip")
+    return (out, y, coef_y, coef_c) if return_coef else (out, y)
 
 
 def _draw(fn, shape, generator: Optional[torch.Generator], device) -> torch.Tensor:

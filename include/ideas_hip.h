@@ -33,6 +33,7 @@
 #ifndef IDEAS_HIP_H
 #define IDEAS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -681,6 +682,60 @@ int ideas_pair_prepare(void* y, const void* x, const int* box, const float* shif
 int ideas_jpeg_roundtrip(void* out_u8, float* y, short* coef, const void* x_u8, int B, int C, int H, int W, int quality, void* stream);
 int ideas_pixel_attack(void* out_u8, float* y, const void* x_u8, const float* noise, const float* u, int B, int C, int H, int W,
                        float gain, float offset, float sigma, float sp, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The JPEG file channel, csrc/attack_jpeg.hip: the bytes a decoder reads out of the JPEG FILE that libjpeg 6b / libjpeg-turbo writes
+ * with its defaults (what Pillow's Image.save(f, "JPEG", quality=Q) runs): the integer "islow" DCT, 4:2:0 or 4:4:4, fancy upsampling,
+ * without the entropy coder (lossless).  Unlike ideas_jpeg_roundtrip above, which is a model in f32 at 4:4:4, all of this is int32 and
+ * the result is defined to the byte: tests/jpegfile_ref.py restates it in numpy and tests/test_jpeg_file.py holds that restatement to
+ * Pillow's own round trip, byte for byte.  x_u8, out_u8, y as in "Channel attacks".  subsampling: 0 = 4:4:4, 2 = 4:2:0 (Pillow's
+ * numbering); checked, but without effect, with C = 1.  coef_y (optional): int16 [B][ceil(H/8)][ceil(W/8)][64].  coef_c (optional, C = 3): int16
+ * [B][2][cbh][cbw][64] (Cb, Cr), the chroma block grid being the luma grid at 4:4:4 and ceil(ceil(H/2)/8) x ceil(ceil(W/2)/8) at
+ * 4:2:0.  Index 8 u + v, u the vertical frequency.  The model:
+ *     1. Colour in: the three fixed-point lines of ideas_jpeg_roundtrip step 1.  C = 1 has one plane.
+ *     2. Quantiser tables T: Annex K with the IJG quality rule, as step 4 there (clamp 1..255).
+ *     3. Chroma at 4:2:0, ch = ceil(H/2), cw = ceil(W/2).  The full-resolution Cb and Cr planes are padded to an even number of rows
+ *        by replicating the last row and to 16 ceil(cw/8) columns by replicating the last column; then
+ *            c(i,j) = (p(2i,2j) + p(2i,2j+1) + p(2i+1,2j) + p(2i+1,2j+1) + bias) >> 2,   bias = 1 for even j, 2 for odd j;
+ *        then the last row of c is replicated down to 8 ceil(ch/8) rows.  The horizontal padding comes BEFORE the average and the
+ *        vertical padding AFTER it: the other orders give other bytes wherever the chroma size is no multiple of 8.
+ *     4. Luma, and chroma at 4:4:4: padded to multiples of 8 by replicating the last row and column.
+ *     5. Forward DCT per 8x8 block on samples - 128, two passes of the 8-point transform below (rows, then columns), constants
+ *        round(c 2^13):  K298 = 2446, K390 = 3196, K541 = 4433, K765 = 6270, K899 = 7373, K1175 = 9633, K1501 = 12299, K1847 = 15137,
+ *        K1961 = 16069, K2053 = 16819, K2562 = 20995, K3072 = 25172;  DESCALE(x, n) = (x + (1 << (n-1))) >> n, arithmetic shift.
+ *            t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4
+ *            t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2,  z = (t12 + t13) K541
+ *            rows:    o0 = (t10 + t11) << 2,       o4 = (t10 - t11) << 2,       n = 11
+ *            columns: o0 = DESCALE(t10 + t11, 2),  o4 = DESCALE(t10 - t11, 2),  n = 15
+ *            o2 = DESCALE(z + t13 K765, n),  o6 = DESCALE(z - t12 K1847, n)
+ *            ODD(t4, t5, t6, t7):  z5 = (t4 + t5 + t6 + t7) K1175,  z1 = -(t4 + t7) K899,  z2 = -(t5 + t6) K2562,
+ *                                  z3 = z5 - (t4 + t6) K1961,  z4 = z5 - (t5 + t7) K390
+ *                                  a4 = t4 K298 + z1 + z3,  a5 = t5 K2053 + z2 + z4,  a6 = t6 K3072 + z2 + z3,  a7 = t7 K1501 + z1 + z4
+ *            o7 = DESCALE(a4, n),  o5 = DESCALE(a5, n),  o3 = DESCALE(a6, n),  o1 = DESCALE(a7, n)
+ *        The result c is 8 F.
+ *     6. Quantiser: q = sign(c) ((|c| + 4 T) / (8 T)), integer division.
+ *     7. Inverse on e = q T, columns (n = 11), then rows (n = 18), then + 128 and the clamp to 0..255:
+ *            z = (e2 + e6) K541,  t2 = z - e6 K1847,  t3 = z + e2 K765,  t0 = (e0 + e4) << 13,  t1 = (e0 - e4) << 13
+ *            t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2,   (a0, a1, a2, a3) = ODD(e7, e5, e3, e1)
+ *            o0, o7 = DESCALE(t10 +- a3, n),  o1, o6 = DESCALE(t11 +- a2, n),  o2, o5 = DESCALE(t12 +- a1, n),  o3, o4 = DESCALE(t13 +- a0, n)
+ *        (The library's range table wraps outside -512..511 before the + 128; no coefficient set an encoder produces gets there, and
+ *        the restatement asserts it.  Every product of both transforms has factors below 2^23 and fits 32 bits; asserted as well.)
+ *     8. Chroma up at 4:2:0, on the ch x cw real samples only, neighbour indices clamped to them:
+ *            s(i,j) = 3 c(i,j) + c(i',j),   i' = i - 1 for output row 2i, i + 1 for output row 2i + 1
+ *            out(., 2j) = (3 s(j) + s(j-1) + 8) >> 4,   out(., 2j+1) = (3 s(j) + s(j+1) + 7) >> 4
+ *        Except with cw <= 2 (W <= 4): the library does not filter then, every chroma sample is copied to its 2x2 pixels.
+ *     9. Colour out: step 7 of ideas_jpeg_roundtrip.
+ * C = 1 and 4:4:4 take one launch and no workspace.  4:2:0 takes two: the first writes the decoded half-resolution Cb and Cr as bytes
+ * [B][2][ch][cw] into `workspace` (ideas_jpeg_file_workspace_bytes: 2 B ch cw there, 0 otherwise, and 0 for arguments the round trip
+ * refuses), the second reads them with clamped neighbours.  Nothing is written outside out_u8, y, coef_y, coef_c and workspace.  With
+ * W % 8 == 0, x_u8 and out_u8 8-byte aligned and y 16-byte aligned a lane moves its 8 pixels as 8-byte words and float4; any other
+ * placement goes byte by byte; the same bytes either way.  Speed: not measured on an MI355X (DESIGN.md "Channel attacks").
+ * IDEAS_E_NULL: x_u8 or out_u8 is NULL, or workspace is NULL where the size query is non-zero.  IDEAS_E_SHAPE: B, H or W <= 0, C other
+ * than 1 or 3.  IDEAS_E_UNSUPPORTED: quality outside 1..100, subsampling other than 0 or 2.  Every check comes before any launch.
+ * (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+size_t ideas_jpeg_file_workspace_bytes(int B, int C, int H, int W, int subsampling);
+int ideas_jpeg_file_roundtrip(void* out_u8, float* y, short* coef_y, short* coef_c, void* workspace, const void* x_u8, int B, int C,
+                              int H, int W, int quality, int subsampling, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Spatial channel attacks on the 8-bit container, csrc/attack_spatial.hip: rescaling, Gaussian filtering and median filtering, what

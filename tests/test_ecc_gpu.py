@@ -215,6 +215,36 @@ def test_viterbi_long_codewords_take_the_workspace():
     assert rc == -3
 
 
+@pytest.mark.parametrize("rate", ["1/2", "3/4"])
+def test_long_interleaver_takes_the_64_bit_products(rate):
+    """Above n = 65536 message bits the de-interleaver's i * P no longer fits 32 bits and the kernel takes the 64-bit product, as the
+    encoder's (kb * 8) * Pinv does: n = 120000 (N = 3, sigma = 8 at 1024 x 1024 gives 98304) has (m - 1) P >= 2^32, so a product
+    truncated to 32 bits lands on another position.  The encoder, the raw decoder with a workspace and ``ecc.decode`` are compared
+    with the REFERENCE's output, not with ``info`` (at 3/4 with this noise the code does not recover it); row 1 of the soft values is
+    pure noise."""
+    from ideas_amd import ecc
+    n, b = 120_000, 2
+    pl = R.plan(n, rate)
+    k, P = pl["k"], pl["P"]
+    assert n > 65536 and (pl["m"] - 1) * P >= 2 ** 32 and ((n + 7) // 8 * 8 - 8) * pl["Pinv"] >= 2 ** 32
+    rng = np.random.default_rng(n + rate_id(rate))
+    info = rng.integers(0, 256, (b, k // 8), dtype=np.uint8)
+    fill = R.pack(rng.integers(0, 2, (b, n)))
+    want = R.encode(info, n, rate, fill)
+    assert np.array_equal(raw_encode(info, n, k, rate, P, pl["Pinv"], fill), want)
+    coded = R.unpack(want, n).astype(np.int32)
+    soft = np.clip((coded * 2 - 1) * 32 + np.rint(rng.normal(0, 16, coded.shape)), -127, 127).astype(np.int8)
+    soft[1] = rng.integers(-128, 128, n).astype(np.int8)
+    want_info, want_metric = R.viterbi(soft, n, k, rate, P)
+    got_info, got_metric = raw_viterbi(soft, n, k, rate, P, True)
+    assert np.array_equal(got_metric, want_metric), (got_metric.tolist(), want_metric.tolist())
+    assert np.array_equal(got_info, want_info)
+    code = ecc.Code(n, rate)
+    assert (code.k_bits, code.stride) == (k, P)
+    dec_info, dec_metric = ecc.decode(code, dev(soft))
+    assert np.array_equal(dec_info.cpu().numpy(), want_info) and np.array_equal(dec_metric.cpu().numpy(), want_metric)
+
+
 # ------------------------------------------------------------------------------------------------- end to end on stand-in networks
 BLOCK = 16
 E2E = SimpleNamespace(N=1, image_size=256, texture_channel=8)          # 16 x 16 elements: n = 256 message bits at sigma = 1

@@ -2,21 +2,12 @@
 // per-pixel attacks (intensity, additive Gaussian noise, salt and pepper) in one streaming launch.  The model of the round trip is
 // stated step by step in include/ideas_hip.h ("Channel attacks") and restated in numpy by tests/attacks_ref.py.
 //
-// Lane mapping of the round trip: eight lanes own one 8x8 block, one row of 8 pixels x C bytes each; a wave owns 8 blocks side by
-// side (8 rows x 64 columns), lane = 8 * row + block, so that lanes 8 r .. 8 r + 7 read one contiguous run of 64 * C bytes of image
-// row r.  The row pass of the DCT runs in registers, the block is transposed through a wave-private LDS tile (stride 72 floats a block:
-// the column reads of a half-wave fall on 32 different banks), the column pass, the quantiser and the dequantiser run in registers
-// with lane = 8 * column + block, and the inverse goes the same way back through a second LDS tile.  DESIGN.md "Channel attacks".
-#include "common.hpp"
+// The round trip's lane mapping, tables, colour conversion, row I/O, tile walk and the block's way through LDS are jpeg_block.hpp's,
+// shared with attack_jpeg.hip; this file holds the f32 model's arithmetic (f32_arith), the kernel's planes and the launchers.  The
+// container's byte stores are u8.hpp's.  DESIGN.md "Channel attacks".
+#include "jpeg_block.hpp"
 
 namespace {
-
-// ISO/IEC 10918-1 Annex K, tables K.1 (luminance) and K.2 (chrominance), index 8 u + v
-__device__ const unsigned char k_annex_k[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 
 // cos(n pi / 16).  The 8-point transforms below are UNNORMALISED: t_k = sum_j b_k(j) x_j with b_0 = 1, b_4 = (+ - - + + - - +) and
 // b_k(j) = cos((2 j + 1) k pi / 16) otherwise; the orthonormal DCT is alpha_k t_k with alpha_0 = alpha_4 = 1 / (2 sqrt 2) and
@@ -26,7 +17,6 @@ constexpr float C1 = 0.98078528040323043f, C2 = 0.92387953251128674f, C3 = 0.831
                 C6 = 0.38268343236508978f, C7 = 0.19509032201612825f;
 constexpr float SCALE_ONE = 0.17677669529663687f;           // alpha_u alpha_v with exactly one index in {0, 4}: 1 / (4 sqrt 2)
 constexpr float SCALE_NONE = 0.25f;                          // ... with none
-constexpr int TILE_LD = 72;                                  // floats from one block's 8x8 LDS tile to the next
 
 __device__ __forceinline__ void fdct8(const float (&x)[8], float (&t)[8]) {
     const float s0 = x[0] + x[7], s1 = x[1] + x[6], s2 = x[2] + x[5], s3 = x[3] + x[4];
@@ -57,21 +47,50 @@ __device__ __forceinline__ void idct8(const float (&e)[8], float (&x)[8]) {
     x[3] = ev3 + o3; x[4] = ev3 - o3;
 }
 
-__device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-// what ideas_image_u8_to_f32(mean 0.5, std 0.5) makes of a byte (csrc/image_io.hip's two steps)
-__device__ __forceinline__ float byte_to_unit(unsigned q) {
-    float t;
-    {
-#pragma clang fp contract(off)
-        t = (float)q / 255.0f;
-        t = (t - 0.5f) / 0.5f;
+// The f32 model as block_roundtrip's arithmetic.  tq: the plane's table; rc: this lane's r as a COLUMN index is 0 or 4
+struct f32_arith {
+    using T = float;
+    const float* tq;
+    bool rc;
+    __device__ __forceinline__ void rows_fwd(const int (&v)[8], float (&g)[8]) const {
+        float a[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = (float)(v[j] - 128);
+        fdct8(a, g);
     }
-    return t;
-}
-
-// byte i (a compile-time index after unrolling) of consecutive little-endian words
-template <int N> __device__ __forceinline__ unsigned byte_of(const unsigned (&w)[N], int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
+    // a[u] becomes the unnormalised T(u, r)
+    __device__ __forceinline__ void cols_fwd(const float (&g)[8], float (&a)[8]) const { fdct8(g, a); }
+    __device__ __forceinline__ void quant_dequant(float (&a)[8], short (&qs)[8], int r) const {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float T = tq[u * 8 + r];
+            const bool ru = u == 0 || u == 4;
+            const float scale = ru ? SCALE_ONE : (rc ? SCALE_ONE : SCALE_NONE);
+            const float F = a[u] * scale;
+            float q = copysignf(floorf(fabsf(F) / T + 0.5f), F);
+            float e = (q * T) * scale;
+            if (ru && rc) {                                  // F = S / 8, S an integer: quantised in integers, dequantised in eighths
+                const int S = (int)a[u], iT = (int)T;
+                const int m = ((S < 0 ? -S : S) + 4 * iT) / (8 * iT);
+                const int qi = S < 0 ? -m : m;
+                q = (float)qi;
+                e = (float)(qi * iT) * 0.125f;
+            }
+            qs[u] = (short)(int)q;
+            a[u] = e;
+        }
+    }
+    __device__ __forceinline__ void cols_inv(const float (&a)[8], float (&g)[8]) const { idct8(a, g); }
+    __device__ __forceinline__ void rows_inv(const float (&a)[8], int (&v)[8]) const {
+        float g[8];
+        idct8(a, g);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float w = floorf((g[j] + 128.0f) + 0.5f);
+            v[j] = (int)fminf(fmaxf(w, 0.0f), 255.0f);
+        }
+    }
+};
 
 // VEC: W % 8 == 0, x and out 8-byte aligned, y 16-byte aligned: a lane's 8 pixels are C 8-byte words and 2 C float4
 template <int C, bool VEC>
@@ -80,176 +99,53 @@ __global__ __launch_bounds__(256) void jpeg_roundtrip_kernel(unsigned char* __re
                                                              int qscale, int64_t ntiles) {
     __shared__ __attribute__((aligned(16))) float s_tile[2][4][8 * TILE_LD];      // [forward | inverse][wave][block][8][8]
     __shared__ float s_q[2][64];
-    __shared__ float s_unit[256];                            // byte -> received f32: its two true divisions once a workgroup, not 8 C times a lane
-    s_unit[threadIdx.x] = byte_to_unit(threadIdx.x);
-    if (threadIdx.x < 128) {                                 // the IJG quality rule on Annex K
-        int t = ((int)k_annex_k[threadIdx.x >> 6][threadIdx.x & 63] * qscale + 50) / 100;
-        s_q[threadIdx.x >> 6][threadIdx.x & 63] = (float)(t < 1 ? 1 : (t > 255 ? 255 : t));
-    }
+    __shared__ float s_unit[256];                            // byte -> received f32, not 8 C times a lane
+    fill_unit(s_unit);
+    if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = (float)jpeg_table_entry(threadIdx.x, qscale);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, blk = lane & 7, r = lane >> 3;
     float* fw = &s_tile[0][wave][blk * TILE_LD];
     float* iv = &s_tile[1][wave][blk * TILE_LD];
     const int bwn = (W + 7) >> 3, bhn = (H + 7) >> 3, txn = (bwn + 7) >> 3;
-    const bool rc = (r & 3) == 0;                            // as a column index: 0 or 4
 
-    // every wave of a workgroup makes the same number of trips (the barriers), a wave past the last tile repeats it without stores
-    for (int64_t t0 = (int64_t)blockIdx.x * 4; t0 < ntiles; t0 += (int64_t)gridDim.x * 4) {
-        const bool live_tile = t0 + wave < ntiles;
-        const int64_t t = live_tile ? t0 + wave : ntiles - 1;
-        const int tx = (int)(t % txn);
-        const int by = (int)((t / txn) % bhn);
-        const int64_t b = t / txn / bhn;
-        const int bx = tx * 8 + blk;
-        const bool live = live_tile && bx < bwn;
-        const int x0 = bx * 8, yy = by * 8 + r;
-        const int64_t row_in = (b * H + (yy < H ? yy : H - 1)) * W;   // replicated last row
+    for (int64_t t0 = tile_first(); t0 < ntiles; t0 += tile_step()) {
+        const jpeg_tile t(t0, wave, lane, ntiles, txn, bhn, bwn);
+        const int64_t row_in = (t.b * H + (t.yy < H ? t.yy : H - 1)) * W;        // replicated last row
 
         int pl[C][8];                                        // the planes: Y (Cb Cr), 0..255
         {
             int px[C][8];
-            if constexpr (VEC) {
-                const int xl = x0 < W ? x0 : W - 8;          // (a lane without a block stays inside the row)
-                unsigned w[2 * C];
-                const uint2* p = reinterpret_cast<const uint2*>(x + (row_in + xl) * C);
-#pragma unroll
-                for (int k = 0; k < C; ++k) { const uint2 v = p[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-#pragma unroll
-                    for (int c = 0; c < C; ++c) px[c][j] = (int)byte_of(w, j * C + c);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int xc = x0 + j < W ? x0 + j : W - 1;      // replicated last column
-                    const unsigned char* p = x + (row_in + xc) * C;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) px[c][j] = p[c];
-                }
-            }
+            load8<C, VEC>(x + row_in * C, t.x0, W, px);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 if constexpr (C == 3) {
-                    const int R = px[0][j], G = px[1][j], Bl = px[2][j];
-                    // (24-bit multiplies: the factors are below 2^17 and 2^8, the products exact)
-                    pl[0][j] = (__mul24(19595, R) + __mul24(38470, G) + __mul24(7471, Bl) + 32768) >> 16;
-                    pl[1][j] = (__mul24(-11059, R) - __mul24(21709, G) + __mul24(32768, Bl) + (128 << 16) + 32767) >> 16;
-                    pl[2][j] = (__mul24(32768, R) - __mul24(27439, G) - __mul24(5329, Bl) + (128 << 16) + 32767) >> 16;
+                    pl[0][j] = luma_of(px[0][j], px[1][j], px[2][j]);
+                    pl[1][j] = cb_of(px[0][j], px[1][j], px[2][j]);
+                    pl[2][j] = cr_of(px[0][j], px[1][j], px[2][j]);
                 } else {
                     pl[0][j] = px[0][j];
                 }
             }
         }
-
 #pragma unroll
         for (int p = 0; p < C; ++p) {
-            const float* tq = s_q[p > 0];
-            float a[8], g[8];
-            // rows: lane = (block, row r)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] = (float)(pl[p][j] - 128);
-            fdct8(a, g);
-            reinterpret_cast<float4*>(fw + r * 8)[0] = make_float4(g[0], g[1], g[2], g[3]);
-            reinterpret_cast<float4*>(fw + r * 8)[1] = make_float4(g[4], g[5], g[6], g[7]);
-            __syncthreads();
-            // columns: lane = (block, column r); a[u] becomes the unnormalised T(u, r)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) g[i] = fw[i * 8 + r];
-            fdct8(g, a);
-            short qs[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float T = tq[u * 8 + r];
-                const bool ru = u == 0 || u == 4;
-                const float scale = ru ? SCALE_ONE : (rc ? SCALE_ONE : SCALE_NONE);
-                const float F = a[u] * scale;
-                float q = copysignf(floorf(fabsf(F) / T + 0.5f), F);
-                float e = (q * T) * scale;
-                if (ru && rc) {                              // F = S / 8, S an integer: quantised in integers, dequantised in eighths
-                    const int S = (int)a[u], iT = (int)T;
-                    const int m = ((S < 0 ? -S : S) + 4 * iT) / (8 * iT);
-                    const int qi = S < 0 ? -m : m;
-                    q = (float)qi;
-                    e = (float)(qi * iT) * 0.125f;
-                }
-                qs[u] = (short)(int)q;
-                a[u] = e;
-            }
-            if (coef && live) {
-                short* cdst = coef + ((((b * C + p) * bhn + by) * bwn + bx) * 64 + r);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) cdst[u * 8] = qs[u];
-            }
-            idct8(a, g);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) iv[i * 8 + r] = g[i];
-            __syncthreads();
-            // rows again
-            {
-                const float4 v0 = reinterpret_cast<const float4*>(iv + r * 8)[0], v1 = reinterpret_cast<const float4*>(iv + r * 8)[1];
-                a[0] = v0.x; a[1] = v0.y; a[2] = v0.z; a[3] = v0.w; a[4] = v1.x; a[5] = v1.y; a[6] = v1.z; a[7] = v1.w;
-            }
-            idct8(a, g);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = floorf((g[j] + 128.0f) + 0.5f);
-                pl[p][j] = (int)fminf(fmaxf(v, 0.0f), 255.0f);
-            }
+            block_roundtrip(pl[p], f32_arith{s_q[p > 0], (r & 3) == 0}, fw, iv, r, coef && t.live,
+                            coef + ((((t.b * C + p) * bhn + t.by) * bwn + t.bx) * 64 + r));
         }
-
         unsigned ob[8 * C];                                  // the bytes of this lane's row, pixel-major
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (C == 3) {
-                const int Y = pl[0][j], cb = pl[1][j] - 128, cr = pl[2][j] - 128;
-                ob[3 * j] = (unsigned)clamp_u8(Y + ((__mul24(91881, cr) + 32768) >> 16));
-                ob[3 * j + 1] = (unsigned)clamp_u8(Y + ((__mul24(-22554, cb) - __mul24(46802, cr) + 32768) >> 16));
-                ob[3 * j + 2] = (unsigned)clamp_u8(Y + ((__mul24(116130, cb) + 32768) >> 16));
-            } else {
-                ob[j] = (unsigned)pl[0][j];
-            }
-        }
-        if (live && yy < H) {
-            const int64_t o = ((b * H + yy) * W + x0) * C;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int k = 0; k < C; ++k) {
-                    uint2 v;
-                    v.x = ob[8 * k] | (ob[8 * k + 1] << 8) | (ob[8 * k + 2] << 16) | (ob[8 * k + 3] << 24);
-                    v.y = ob[8 * k + 4] | (ob[8 * k + 5] << 8) | (ob[8 * k + 6] << 16) | (ob[8 * k + 7] << 24);
-                    reinterpret_cast<uint2*>(out + o)[k] = v;
-                }
-                if (y) {
-#pragma unroll
-                    for (int k = 0; k < 2 * C; ++k)
-                        reinterpret_cast<float4*>(y + o)[k] = make_float4(s_unit[ob[4 * k]], s_unit[ob[4 * k + 1]], s_unit[ob[4 * k + 2]],
-                                                                          s_unit[ob[4 * k + 3]]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (x0 + j < W) {
-#pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            out[o + j * C + c] = (unsigned char)ob[j * C + c];
-                            if (y) y[o + j * C + c] = s_unit[ob[j * C + c]];
-                        }
-                    }
-                }
-            }
-        }
+        ycc_to_rgb<C>(pl, ob);
+        if (t.live && t.yy < H) store8<C, VEC>(out, y, ((t.b * H + t.yy) * W + t.x0) * C, ob, t.x0, W, s_unit);
     }
 }
 
 template <int C>
 int launch_jpeg(void* out, float* y, short* coef, const void* x, int B, int H, int W, int quality, hipStream_t stream) {
-    const int qscale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int qscale = jpeg_qscale(quality);
     const int64_t bwn = (W + 7) / 8, bhn = (H + 7) / 8;
     const int64_t ntiles = (int64_t)B * bhn * ideas_cdiv(bwn, 8);
     int64_t grid = ideas_cdiv(ntiles, 4);
     if (grid > 16384) grid = 16384;
-    const bool vec = W % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
-                     ideas_aligned16(y);
+    const bool vec = W % 8 == 0 && ideas_aligned<8>(x) && ideas_aligned<8>(out) && ideas_aligned16(y);
     if (vec)
         hipLaunchKernelGGL((jpeg_roundtrip_kernel<C, true>), dim3((unsigned)grid), dim3(256), 0, stream, (unsigned char*)out, y, coef,
                            (const unsigned char*)x, H, W, qscale, ntiles);
@@ -317,12 +213,7 @@ __global__ __launch_bounds__(256) void pixel_attack_kernel(unsigned char* __rest
                 if (u) ob[e] = salt_pepper(ob[e], uu[e / C], lo, hi);
             }
 #pragma unroll
-            for (int k = 0; k < C; ++k) {
-                reinterpret_cast<unsigned*>(out)[q * C + k] = ob[4 * k] | (ob[4 * k + 1] << 8) | (ob[4 * k + 2] << 16) | (ob[4 * k + 3] << 24);
-                if (y)
-                    reinterpret_cast<float4*>(y)[q * C + k] = make_float4(byte_to_unit(ob[4 * k]), byte_to_unit(ob[4 * k + 1]),
-                                                                          byte_to_unit(ob[4 * k + 2]), byte_to_unit(ob[4 * k + 3]));
-            }
+            for (int k = 0; k < C; ++k) store_bytes<4, 4>(out, y, (q * C + k) * 4, ob + 4 * k, 4, unit_direct{});     // word by word
         }
         done = nq << 2;
     }
@@ -341,8 +232,7 @@ __global__ __launch_bounds__(256) void pixel_attack_kernel(unsigned char* __rest
 template <int C>
 int launch_pixel(void* out, float* y, const void* x, const float* noise, const float* u, int64_t npix, float gain, float offset,
                  float sigma, float sp, hipStream_t stream) {
-    const bool vec = npix >= 4 && (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
-                     ideas_aligned16(y) && ideas_aligned16(noise) && ideas_aligned16(u);
+    const bool vec = npix >= 4 && ideas_aligned<4>(x) && ideas_aligned<4>(out) && ideas_aligned16(y) && ideas_aligned16(noise) && ideas_aligned16(u);
     int64_t grid = ideas_cdiv(vec ? npix >> 2 : npix, 256);
     if (grid > 16384) grid = 16384;
     if (vec)

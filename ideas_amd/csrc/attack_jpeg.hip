@@ -3,34 +3,24 @@
 // coder.  All of it is int32, so the result is defined to the byte.  The model is stated step by step in include/ideas_hip.h ("The
 // JPEG file channel") and restated in numpy by tests/jpegfile_ref.py, which tests/test_jpeg_file.py holds to Pillow's own bytes.
 //
-// Lane mapping, as in attack.hip: eight lanes own one 8x8 block, one row of 8 samples each; a wave owns 8 blocks side by side, lane =
-// 8 * row + block.  The row pass of a transform runs in registers, the block is transposed through a wave-private LDS tile (stride 72
-// ints a block), the column pass, the quantiser and the dequantiser run in registers with lane = 8 * column + block, and the inverse
-// goes the same way back through a second tile.
+// The lane mapping, tables, colour conversion, row I/O, tile walk and the block's way through LDS are jpeg_block.hpp's, shared with
+// attack.hip; this file holds the integer model's arithmetic (islow_arith), the kernels' plane logic (the 4:2:0 average, the triangle
+// upsampler) and the launchers.
 //
 // 4:2:0 takes two launches, because the upsampler needs one chroma sample of halo across block borders: chroma420_kernel loads 16x16
 // pixels a block, converts, averages, round-trips Cb and Cr and writes the decoded half-resolution planes as bytes into the workspace;
 // jpeg_file_kernel round-trips the luma, reads the workspace with clamped neighbours, upsamples, converts and stores.  4:4:4 and C = 1
 // are jpeg_file_kernel alone.  DESIGN.md "Channel attacks".
-#include "common.hpp"
+#include "jpeg_block.hpp"
 
 namespace {
-
-// ISO/IEC 10918-1 Annex K, tables K.1 (luminance) and K.2 (chrominance), index 8 u + v
-__device__ const unsigned char k_annex_k[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 
 // round(c * 2^13) of the twelve constants of the 8-point transform
 constexpr int F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633;
 constexpr int F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
 constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-constexpr int TILE_LD = 72;                                  // ints from one block's 8x8 LDS tile to the next
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-__device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // The odd half both transforms share: (t4, t5, t6, t7) -> four rotated sums.  Every factor stays below 2^23 and every product below
 // 2^31 for what an encoder produces (tests/jpegfile_ref.py asserts it on every product), so the 24-bit multiply is exact.
@@ -90,105 +80,45 @@ __device__ __forceinline__ int quantise(int c, int den, float rden) {
     return c < 0 ? -q : q;
 }
 
-// what ideas_image_u8_to_f32(mean 0.5, std 0.5) makes of a byte (csrc/image_io.hip's two steps)
-__device__ __forceinline__ float byte_to_unit(unsigned q) {
-    float t;
-    {
-#pragma clang fp contract(off)
-        t = (float)q / 255.0f;
-        t = (t - 0.5f) / 0.5f;
-    }
-    return t;
-}
-
-// byte i (a compile-time index after unrolling) of consecutive little-endian words
-template <int N> __device__ __forceinline__ unsigned byte_of(const unsigned (&w)[N], int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
-
 // the IJG quality rule on Annex K: s_t the tables, s_d = 8 T and s_r = 1 / (8 T) for the quantiser; threads 0..127 of the workgroup
 __device__ __forceinline__ void fill_tables(int (*s_t)[64], int (*s_d)[64], float (*s_r)[64], int qscale) {
     if (threadIdx.x < 128) {
-        int t = ((int)k_annex_k[threadIdx.x >> 6][threadIdx.x & 63] * qscale + 50) / 100;
-        t = t < 1 ? 1 : (t > 255 ? 255 : t);
+        const int t = jpeg_table_entry(threadIdx.x, qscale);
         s_t[threadIdx.x >> 6][threadIdx.x & 63] = t;
         s_d[threadIdx.x >> 6][threadIdx.x & 63] = 8 * t;
         s_r[threadIdx.x >> 6][threadIdx.x & 63] = 1.0f / (float)(8 * t);
     }
 }
 
-// 8 pixels of one image row (row = x + row offset in bytes) from column x0 on.  VEC (W % 8 == 0, 8-byte aligned rows): C 8-byte
-// words, a lane past the row reads its last 8 pixels; otherwise byte by byte with the last column replicated.
-template <int C, bool VEC> __device__ __forceinline__ void load8(const unsigned char* __restrict__ row, int x0, int W, int (&px)[C][8]) {
-    if constexpr (VEC) {
-        const int xl = x0 < W ? x0 : W - 8;
-        unsigned w[2 * C];
-        const uint2* p = reinterpret_cast<const uint2*>(row + (int64_t)xl * C);
+// The integer model as block_roundtrip's arithmetic.  tq, dq, rq: the plane's T, 8 T and 1 / (8 T)
+struct islow_arith {
+    using T = int;
+    const int *tq, *dq;
+    const float* rq;
+    __device__ __forceinline__ void rows_fwd(const int (&v)[8], int (&g)[8]) const {
+        int a[8];
 #pragma unroll
-        for (int k = 0; k < C; ++k) { const uint2 v = p[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
+        for (int j = 0; j < 8; ++j) a[j] = v[j] - 128;
+        fdct_pass<true>(a, g);
+    }
+    // a[u] becomes 8 F(u, r)
+    __device__ __forceinline__ void cols_fwd(const int (&g)[8], int (&a)[8]) const { fdct_pass<false>(g, a); }
+    __device__ __forceinline__ void quant_dequant(int (&a)[8], short (&qs)[8], int r) const {
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int c = 0; c < C; ++c) px[c][j] = (int)byte_of(w, j * C + c);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int xc = x0 + j < W ? x0 + j : W - 1;
-            const unsigned char* p = row + (int64_t)xc * C;
-#pragma unroll
-            for (int c = 0; c < C; ++c) px[c][j] = p[c];
+        for (int u = 0; u < 8; ++u) {
+            const int q = quantise(a[u], dq[u * 8 + r], rq[u * 8 + r]);
+            qs[u] = (short)q;
+            a[u] = __mul24(q, tq[u * 8 + r]);
         }
     }
-}
-
-// (24-bit multiplies: the factors are below 2^17 and 2^8, the products exact)
-__device__ __forceinline__ int luma_of(int R, int G, int Bl) { return (__mul24(19595, R) + __mul24(38470, G) + __mul24(7471, Bl) + 32768) >> 16; }
-__device__ __forceinline__ int cb_of(int R, int G, int Bl) {
-    return (__mul24(-11059, R) - __mul24(21709, G) + __mul24(32768, Bl) + (128 << 16) + 32767) >> 16;
-}
-__device__ __forceinline__ int cr_of(int R, int G, int Bl) {
-    return (__mul24(32768, R) - __mul24(27439, G) - __mul24(5329, Bl) + (128 << 16) + 32767) >> 16;
-}
-
-// One plane's 8x8 block through forward DCT, quantiser, dequantiser and inverse: v = this lane's row r of samples 0..255 in, the decoded
-// row out.  fw, iv: the block's two LDS tiles; tq, dq, rq: the plane's T, 8 T and 1 / (8 T); cdst (or null): the block's 64 coefficients
-// + r.  Two workgroup barriers: every wave of the workgroup calls this the same number of times.
-__device__ __forceinline__ void plane_roundtrip(int (&v)[8], const int* tq, const int* dq, const float* rq, int* fw, int* iv, int r,
-                                                short* __restrict__ cdst) {
-    int a[8], g[8];
-    // rows: lane = (block, row r)
+    __device__ __forceinline__ void cols_inv(const int (&a)[8], int (&g)[8]) const { idct_pass<true>(a, g); }
+    __device__ __forceinline__ void rows_inv(const int (&a)[8], int (&v)[8]) const {
+        int g[8];
+        idct_pass<false>(a, g);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = v[j] - 128;
-    fdct_pass<true>(a, g);
-    reinterpret_cast<int4*>(fw + r * 8)[0] = make_int4(g[0], g[1], g[2], g[3]);
-    reinterpret_cast<int4*>(fw + r * 8)[1] = make_int4(g[4], g[5], g[6], g[7]);
-    __syncthreads();
-    // columns: lane = (block, column r); a[u] becomes 8 F(u, r)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) g[i] = fw[i * 8 + r];
-    fdct_pass<false>(g, a);
-    short qs[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int q = quantise(a[u], dq[u * 8 + r], rq[u * 8 + r]);
-        qs[u] = (short)q;
-        a[u] = __mul24(q, tq[u * 8 + r]);
+        for (int j = 0; j < 8; ++j) v[j] = clamp_u8(g[j] + 128);
     }
-    if (cdst) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) cdst[u * 8] = qs[u];
-    }
-    idct_pass<true>(a, g);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) iv[i * 8 + r] = g[i];
-    __syncthreads();
-    // rows again
-    {
-        const int4 v0 = reinterpret_cast<const int4*>(iv + r * 8)[0], v1 = reinterpret_cast<const int4*>(iv + r * 8)[1];
-        a[0] = v0.x; a[1] = v0.y; a[2] = v0.z; a[3] = v0.w; a[4] = v1.x; a[5] = v1.y; a[6] = v1.z; a[7] = v1.w;
-    }
-    idct_pass<false>(a, g);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = clamp_u8(g[j] + 128);
-}
+};
 
 // 4:2:0, launch one.  A wave owns 8 chroma blocks side by side; lane (block, r) owns chroma row 8 cby + r, 8 samples: 2 x 16 pixels.
 // half: uint8 [B][2][ch][cw], the decoded Cb and Cr.  coef (or null): int16 [B][2][cbhn][cbwn][64].
@@ -206,16 +136,11 @@ __global__ __launch_bounds__(256) void chroma420_kernel(unsigned char* __restric
     const int ch = (H + 1) >> 1, cw = (W + 1) >> 1;
     const int cbwn = (cw + 7) >> 3, cbhn = (ch + 7) >> 3, txn = (cbwn + 7) >> 3;
 
-    // every wave of a workgroup makes the same number of trips (the barriers), a wave past the last tile repeats it without stores
-    for (int64_t t0 = (int64_t)blockIdx.x * 4; t0 < ntiles; t0 += (int64_t)gridDim.x * 4) {
-        const bool live_tile = t0 + wave < ntiles;
-        const int64_t t = live_tile ? t0 + wave : ntiles - 1;
-        const int tx = (int)(t % txn);
-        const int cby = (int)((t / txn) % cbhn);
-        const int64_t b = t / txn / cbhn;
-        const int cbx = tx * 8 + blk;
-        const bool live = live_tile && cbx < cbwn;
-        const int cy = cby * 8 + r;
+    for (int64_t t0 = tile_first(); t0 < ntiles; t0 += tile_step()) {
+        const jpeg_tile t(t0, wave, lane, ntiles, txn, cbhn, cbwn);          // the walk over CHROMA blocks
+        const int64_t b = t.b;
+        const int cby = t.by, cbx = t.bx, cy = t.yy;
+        const bool live = t.live;
         const int cyc = cy < ch ? cy : ch - 1;               // rows below the last chroma row repeat it: AFTER the average
         const int x0 = cbx * 16;                             // columns right of the image repeat the last column: BEFORE it
 
@@ -249,8 +174,8 @@ __global__ __launch_bounds__(256) void chroma420_kernel(unsigned char* __restric
         for (int p = 0; p < 2; ++p) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) pl[p][k] >>= 2;
-            short* cdst = coef && live ? coef + ((((b * 2 + p) * cbhn + cby) * cbwn + cbx) * 64 + r) : nullptr;
-            plane_roundtrip(pl[p], s_t[1], s_d[1], s_r[1], fw, iv, r, cdst);
+            block_roundtrip(pl[p], islow_arith{s_t[1], s_d[1], s_r[1]}, fw, iv, r, coef && live,
+                            coef + ((((b * 2 + p) * cbhn + cby) * cbwn + cbx) * 64 + r));
             if (live && cy < ch) {
                 unsigned char* dst = half + ((b * 2 + p) * ch + cy) * cw + cbx * 8;
 #pragma unroll
@@ -270,8 +195,8 @@ __global__ __launch_bounds__(256) void jpeg_file_kernel(unsigned char* __restric
     __shared__ __attribute__((aligned(16))) int s_tile[2][4][8 * TILE_LD];
     __shared__ int s_t[2][64], s_d[2][64];
     __shared__ float s_r[2][64];
-    __shared__ float s_unit[256];                            // byte -> received f32: its two true divisions once a workgroup
-    s_unit[threadIdx.x] = byte_to_unit(threadIdx.x);
+    __shared__ float s_unit[256];                            // byte -> received f32
+    fill_unit(s_unit);
     fill_tables(s_t, s_d, s_r, qscale);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, blk = lane & 7, r = lane >> 3;
@@ -280,15 +205,11 @@ __global__ __launch_bounds__(256) void jpeg_file_kernel(unsigned char* __restric
     const int bwn = (W + 7) >> 3, bhn = (H + 7) >> 3, txn = (bwn + 7) >> 3;
     constexpr int NP = (C == 3 && SUB == 0) ? 3 : 1;         // planes that make the round trip here
 
-    for (int64_t t0 = (int64_t)blockIdx.x * 4; t0 < ntiles; t0 += (int64_t)gridDim.x * 4) {
-        const bool live_tile = t0 + wave < ntiles;
-        const int64_t t = live_tile ? t0 + wave : ntiles - 1;
-        const int tx = (int)(t % txn);
-        const int by = (int)((t / txn) % bhn);
-        const int64_t b = t / txn / bhn;
-        const int bx = tx * 8 + blk;
-        const bool live = live_tile && bx < bwn;
-        const int x0 = bx * 8, yy = by * 8 + r;
+    for (int64_t t0 = tile_first(); t0 < ntiles; t0 += tile_step()) {
+        const jpeg_tile t(t0, wave, lane, ntiles, txn, bhn, bwn);
+        const int64_t b = t.b;
+        const int by = t.by, bx = t.bx, x0 = t.x0, yy = t.yy;
+        const bool live = t.live;
         const int64_t row_in = (b * H + (yy < H ? yy : H - 1)) * W;   // replicated last row
 
         int pl[3][8];                                        // Y (Cb Cr), 0..255
@@ -310,13 +231,10 @@ __global__ __launch_bounds__(256) void jpeg_file_kernel(unsigned char* __restric
         }
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            short* cdst = nullptr;
-            if (p == 0) {
-                if (coef_y && live) cdst = coef_y + (((b * bhn + by) * bwn + bx) * 64 + r);
-            } else {
-                if (coef_c && live) cdst = coef_c + ((((b * 2 + (p - 1)) * bhn + by) * bwn + bx) * 64 + r);
-            }
-            plane_roundtrip(pl[p], s_t[p > 0], s_d[p > 0], s_r[p > 0], fw, iv, r, cdst);
+            short* const coef = p == 0 ? coef_y : coef_c;           // [B][1][bhn][bwn][64] and [B][2][bhn][bwn][64]
+            const int64_t plane = p == 0 ? b : b * 2 + (p - 1);
+            block_roundtrip(pl[p], islow_arith{s_t[p > 0], s_d[p > 0], s_r[p > 0]}, fw, iv, r, coef && live,
+                            coef + (((plane * bhn + by) * bwn + bx) * 64 + r));
         }
         if constexpr (C == 3 && SUB == 2) {
             // the triangle filter on the REAL ch x cw samples, neighbours clamped to them: s = 3 c(i, .) + c(i', .), i' the row above
@@ -347,46 +265,8 @@ __global__ __launch_bounds__(256) void jpeg_file_kernel(unsigned char* __restric
         }
 
         unsigned ob[8 * C];                                  // the bytes of this lane's row, pixel-major
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (C == 3) {
-                const int Y = pl[0][j], cb = pl[1][j] - 128, cr = pl[2][j] - 128;
-                ob[3 * j] = (unsigned)clamp_u8(Y + ((__mul24(91881, cr) + 32768) >> 16));
-                ob[3 * j + 1] = (unsigned)clamp_u8(Y + ((__mul24(-22554, cb) - __mul24(46802, cr) + 32768) >> 16));
-                ob[3 * j + 2] = (unsigned)clamp_u8(Y + ((__mul24(116130, cb) + 32768) >> 16));
-            } else {
-                ob[j] = (unsigned)pl[0][j];
-            }
-        }
-        if (live && yy < H) {
-            const int64_t o = ((b * H + yy) * W + x0) * C;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int k = 0; k < C; ++k) {
-                    uint2 v;
-                    v.x = ob[8 * k] | (ob[8 * k + 1] << 8) | (ob[8 * k + 2] << 16) | (ob[8 * k + 3] << 24);
-                    v.y = ob[8 * k + 4] | (ob[8 * k + 5] << 8) | (ob[8 * k + 6] << 16) | (ob[8 * k + 7] << 24);
-                    reinterpret_cast<uint2*>(out + o)[k] = v;
-                }
-                if (y) {
-#pragma unroll
-                    for (int k = 0; k < 2 * C; ++k)
-                        reinterpret_cast<float4*>(y + o)[k] = make_float4(s_unit[ob[4 * k]], s_unit[ob[4 * k + 1]], s_unit[ob[4 * k + 2]],
-                                                                          s_unit[ob[4 * k + 3]]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (x0 + j < W) {
-#pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            out[o + j * C + c] = (unsigned char)ob[j * C + c];
-                            if (y) y[o + j * C + c] = s_unit[ob[j * C + c]];
-                        }
-                    }
-                }
-            }
-        }
+        ycc_to_rgb<C>(pl, ob);
+        if (live && yy < H) store8<C, VEC>(out, y, ((b * H + yy) * W + x0) * C, ob, x0, W, s_unit);
     }
 }
 
@@ -398,8 +278,8 @@ unsigned grid_for(int64_t ntiles) {
 template <int C, int SUB>
 int launch_file(void* out, float* y, short* coef_y, short* coef_c, void* workspace, const void* x, int B, int H, int W, int quality,
                 hipStream_t stream) {
-    const int qscale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-    const bool x8 = W % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 7u) == 0;
+    const int qscale = jpeg_qscale(quality);
+    const bool x8 = W % 8 == 0 && ideas_aligned<8>(x);
     if constexpr (C == 3 && SUB == 2) {
         const int64_t ch = (H + 1) / 2, cw = (W + 1) / 2;
         const int64_t ntiles = (int64_t)B * ideas_cdiv(ch, 8) * ideas_cdiv(ideas_cdiv(cw, 8), 8);
@@ -413,7 +293,7 @@ int launch_file(void* out, float* y, short* coef_y, short* coef_c, void* workspa
         if (rc != IDEAS_OK) return rc;
     }
     const int64_t ntiles = (int64_t)B * ideas_cdiv(H, 8) * ideas_cdiv(ideas_cdiv(W, 8), 8);
-    const bool vec = x8 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && ideas_aligned16(y);
+    const bool vec = x8 && ideas_aligned<8>(out) && ideas_aligned16(y);
     if (vec)
         hipLaunchKernelGGL((jpeg_file_kernel<C, SUB, true>), dim3(grid_for(ntiles)), dim3(256), 0, stream, (unsigned char*)out, y, coef_y,
                            coef_c, (const unsigned char*)workspace, (const unsigned char*)x, H, W, qscale, ntiles);

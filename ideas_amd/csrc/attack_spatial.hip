@@ -7,7 +7,7 @@
 // one float4 of y): byte q of the row is channel q % C of pixel q / C, and a tile starts at a multiple of 64 pixels, so a thread's word
 // is 4-byte aligned in the row whatever C is.  Every LDS array is made of such words: lanes next to each other read and write words
 // next to each other (consecutive banks), no lane touches a single byte of LDS.
-#include "common.hpp"
+#include "u8.hpp"
 
 namespace {
 
@@ -21,41 +21,8 @@ constexpr int MTH = 16;                                      // output rows of a
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// what ideas_image_u8_to_f32(mean 0.5, std 0.5) makes of a byte (csrc/image_io.hip's two steps)
-__device__ __forceinline__ float byte_to_unit(unsigned q) {
-    float t;
-    {
-#pragma clang fp contract(off)
-        t = (float)q / 255.0f;
-        t = (t - 0.5f) / 0.5f;
-    }
-    return t;
-}
-
-// byte i (a compile-time index after unrolling) of consecutive little-endian words
-template <int N> __device__ __forceinline__ unsigned byte_of(const unsigned (&w)[N], int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
-
 // the end of a pass: the sum (which started at 2^21) as a signed 32-bit integer, >> 22, clamped to a byte
-__device__ __forceinline__ unsigned pass_byte(unsigned s) { return (unsigned)clampi((int)s >> 22, 0, 255); }
-
-// the first `nvalid` (1..4; VEC: 4) of four consecutive bytes at byte offset o of out, and of y.  VEC: o % 4 == 0, out 4-byte and y
-// 16-byte aligned
-template <bool VEC>
-__device__ __forceinline__ void store4(unsigned char* __restrict__ out, float* __restrict__ y, int64_t o, int nvalid,
-                                       const unsigned (&b)[4], const float* s_unit) {
-    if constexpr (VEC) {
-        *reinterpret_cast<unsigned*>(out + o) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-        if (y) *reinterpret_cast<float4*>(y + o) = make_float4(s_unit[b[0]], s_unit[b[1]], s_unit[b[2]], s_unit[b[3]]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (e < nvalid) {
-                out[o + e] = (unsigned char)b[e];
-                if (y) y[o + e] = s_unit[b[e]];
-            }
-        }
-    }
-}
+__device__ __forceinline__ unsigned pass_byte(unsigned s) { return (unsigned)clamp_u8((int)s >> 22); }
 
 // ---- resampling -------------------------------------------------------------------------------------------------------------------
 // word d of the tile's part of the horizontal pass of one input row: four bytes, each its own pixel's window.  src holds the row's
@@ -97,7 +64,7 @@ __global__ __launch_bounds__(256) void resample_kernel(unsigned char* __restrict
     __shared__ int s_hkk[KMAX * TW], s_vkk[TH * VK_LD], s_hlo[TW], s_vlo[TH];
     __shared__ float s_unit[256];
     const int tid = threadIdx.x;
-    s_unit[tid] = byte_to_unit(tid);
+    fill_unit(s_unit);
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int tx = (int)(tile % txn), ty = (int)((tile / txn) % tyn);
@@ -182,7 +149,7 @@ __global__ __launch_bounds__(256) void resample_kernel(unsigned char* __restrict
             }
             const unsigned ob[4] = {pass_byte(s[0]), pass_byte(s[1]), pass_byte(s[2]), pass_byte(s[3])};
             const int64_t o = ((b * H2 + oy0 + orow) * W2 + ox0) * C + 4 * d;
-            store4<VEC>(out, y, o, nvalid, ob, s_unit);
+            store_bytes<4, VEC ? 4 : 0>(out, y, o, ob, nvalid, unit_table{s_unit});    // VEC: nvalid is 4 in every word
         }
     }
 }
@@ -195,8 +162,8 @@ int launch_resample(void* out, float* y, const void* x, int B, int H, int W, int
     const int tyn = (int)ideas_cdiv(H2, TH), txn = (int)ideas_cdiv(W2, TW);
     const int64_t ntiles = (int64_t)B * tyn * txn;
     // four bytes a store: every output row starts on a 4-byte boundary and ends on one
-    const bool vec = ((int64_t)W2 * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && ideas_aligned16(y);
-    const bool vin = ((int64_t)W * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 3u) == 0;      // every input row starts on a word
+    const bool vec = ((int64_t)W2 * C) % 4 == 0 && ideas_aligned<4>(out) && ideas_aligned16(y);
+    const bool vin = ((int64_t)W * C) % 4 == 0 && ideas_aligned<4>(x);      // every input row starts on a word
     if (vec)
         hipLaunchKernelGGL((resample_kernel<C, true>), dim3(tile_grid(ntiles)), dim3(256), 0, stream, (unsigned char*)out, y,
                            (const unsigned char*)x, H, W, H2, W2, h_lo, h_kk, hk, v_lo, v_kk, vk, tyn, txn, ntiles, vin);
@@ -259,7 +226,7 @@ __global__ __launch_bounds__(256) void median_kernel(unsigned char* __restrict__
     __shared__ unsigned s_t[SR * PD];
     __shared__ float s_unit[256];
     const int tid = threadIdx.x;
-    s_unit[tid] = byte_to_unit(tid);
+    fill_unit(s_unit);
     const int64_t rowb = (int64_t)W * C;
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -309,7 +276,7 @@ __global__ __launch_bounds__(256) void median_kernel(unsigned char* __restrict__
                 else ob[e] = median_select(v);
             }
             const int64_t o = ((b * H + oy0 + orow) * W + ox0) * C + 4 * d;
-            store4<VEC>(out, y, o, nvalid, ob, s_unit);
+            store_bytes<4, VEC ? 4 : 0>(out, y, o, ob, nvalid, unit_table{s_unit});    // VEC: nvalid is 4 in every word
         }
     }
 }
@@ -318,8 +285,7 @@ template <int C, int K>
 int launch_median(void* out, float* y, const void* x, int B, int H, int W, hipStream_t stream) {
     const int tyn = (int)ideas_cdiv(H, MTH), txn = (int)ideas_cdiv(W, TW);
     const int64_t ntiles = (int64_t)B * tyn * txn;
-    const bool vec = ((int64_t)W * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && ideas_aligned16(y);
+    const bool vec = ((int64_t)W * C) % 4 == 0 && ideas_aligned<4>(out) && ideas_aligned<4>(x) && ideas_aligned16(y);
     if (vec)
         hipLaunchKernelGGL((median_kernel<C, K, true>), dim3(tile_grid(ntiles)), dim3(256), 0, stream, (unsigned char*)out, y,
                            (const unsigned char*)x, H, W, tyn, txn, ntiles);

@@ -11,7 +11,9 @@ static inline int ideas_launch_status() {
     return e == hipSuccess ? IDEAS_OK : (int)e;
 }
 
-static inline bool ideas_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// p on a multiple of N bytes (N a power of two); a null pointer is aligned
+template <unsigned N> static inline bool ideas_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (N - 1u)) == 0; }
+static inline bool ideas_aligned16(const void* p) { return ideas_aligned<16>(p); }
 
 static inline int64_t ideas_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

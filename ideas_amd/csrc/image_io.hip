@@ -1,7 +1,8 @@
 // Input pipeline, device side: decoded images arrive as uint8 HWC (what PIL hands out); one kernel
 // does torchvision's ToTensor + Normalize((0.5,)*3, (0.5,)*3) + the per-sample RandomHorizontalFlip of train.py:443-449 and
 // writes the f32 NHWC activation layout of the networks.  Same operation order as the reference's transforms
-// (v/255, then (v - 0.5) / 0.5), so the result is bit-identical to the CPU pipeline.
+// (v/255, then (v - 0.5) / 0.5), so the result is bit-identical to the CPU pipeline.  The kernels that write the 8-bit container
+// state these two steps as csrc/u8.hpp::byte_to_unit, which must equal them at mean = stdv = 0.5.
 #include "common.hpp"
 
 namespace {

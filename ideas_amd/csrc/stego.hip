@@ -9,6 +9,7 @@
 // Every arithmetic step is one f32 operation in the reference's order (no contraction), so the results are bitwise those of the host
 // functions: see DESIGN.md "Steganography codec".
 #include "stream.hpp"
+#include "u8.hpp"
 
 namespace {
 
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void tensor_to_bits_kernel(unsigned char* __re
     if (threadIdx.x == 0) n_err[b] = part[0] + part[1] + part[2] + part[3];
 }
 
-// one value through the file: the byte that is written, and what a reader's ToTensor + Normalize(0.5, 0.5) makes of it
+// one value through the file: the byte that is written (what a reader's ToTensor + Normalize(0.5, 0.5) makes of it: u8.hpp's byte_to_unit)
 __device__ __forceinline__ unsigned quant1(float x) {
     float t;
     {
@@ -106,15 +107,6 @@ __device__ __forceinline__ unsigned quant1(float x) {
         t = fminf(fmaxf(t, 0.0f), 255.0f);
     }
     return (unsigned)(int)t;
-}
-__device__ __forceinline__ float dequant1(unsigned q) {
-    float t;
-    {
-#pragma clang fp contract(off)
-        t = (float)q / 255.0f;                             // image_io.hip's two steps with mean = stdv = 0.5
-        t = (t - 0.5f) / 0.5f;
-    }
-    return t;
 }
 
 __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -132,9 +124,11 @@ __global__ __launch_bounds__(256) void image_to_u8_flat_kernel(unsigned char* __
         constexpr int U = 4;
         const int64_t nq = n >> 2;
         auto emit = [&](int64_t q, float4 v) {
-            const unsigned a = quant1(v.x), b = quant1(v.y), c = quant1(v.z), d = quant1(v.w);
-            reinterpret_cast<unsigned*>(u8)[q] = a | (b << 8) | (c << 16) | (d << 24);
-            if (y) reinterpret_cast<float4*>(y)[q] = make_float4(dequant1(a), dequant1(b), dequant1(c), dequant1(d));
+            const unsigned b[4] = {quant1(v.x), quant1(v.y), quant1(v.z), quant1(v.w)};
+            // (store_bytes' two stores in this kernel's own form, indexed by the quad: through the byte offset the four groups in
+            // flight are scheduled otherwise, 16 instructions more -- DESIGN.md 8.8)
+            reinterpret_cast<unsigned*>(u8)[q] = pack4(b);
+            if (y) reinterpret_cast<float4*>(y)[q] = make_float4(byte_to_unit(b[0]), byte_to_unit(b[1]), byte_to_unit(b[2]), byte_to_unit(b[3]));
         };
         for (int64_t q0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x; q0 < nq; q0 += stride * U) {
             if (q0 + (U - 1) * 256 < nq) {                 // a whole group: every load is issued before the first use
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(256) void image_to_u8_flat_kernel(unsigned char* __
     for (int64_t i = done + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const unsigned q = quant1(ld1(x + i));
         u8[i] = (unsigned char)q;
-        if (y) y[i] = dequant1(q);
+        if (y) y[i] = byte_to_unit(q);
     }
 }
 
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(256) void image_to_u8_planar_kernel(unsigned char* 
         for (int c = 0; c < C; ++c) {
             const unsigned q = quant1(ld1(src + c * hw));
             u8[p * C + c] = (unsigned char)q;
-            if (y) y[p * C + c] = dequant1(q);
+            if (y) y[p * C + c] = byte_to_unit(q);
         }
     }
 }

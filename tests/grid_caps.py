@@ -139,8 +139,6 @@ CAPS = {
 # ``if (grid > 0x7fffffffLL) return IDEAS_E_SHAPE;`` and ``> MAXSEG`` are checks that assign nothing, and the search does not hit them.
 #   (file, text the line contains): why
 EXCLUDED = {
-    ("attack.hip", "> 255 ? 255 :"): "a value clamped to a byte, in a kernel",
-    ("attack_jpeg.hip", "> 255 ? 255 :"): "a value clamped to a byte, in a kernel",
     ("attack_jpeg.hip", "(rem < 0 ? 1 : 0)"): "the rounding step of an integer division",
     ("stego.hip", "nbit - j0 < 8 ? nbit - j0 : 8"): "the message bits of one byte, in a kernel",
     ("linear.hip", "splits > 64 ? 64 : splits"): "the number of split-K slices: a second grid dimension, every slice one trip",

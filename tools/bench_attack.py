@@ -8,10 +8,12 @@ per-call time.  The calls of a window rotate over ``--sets`` input tensors.  The
 B*H*W*C*(1 + 1 + 4), over the measured HBM copy rate.  The results are compared at the timed size.  Needs a GPU.
 
 The spatial attacks (``op.resize_u8`` to half size and back -- the two launches of ``scale:0.5`` --, ``op.gaussian_blur_u8`` and
-``op.median_u8``) are timed the same way at the same size, through their ops, and written to ``--spatial_out``.
+``op.median_u8``) are timed the same way at the same size, through their ops, and written to ``--spatial_out``; so are the JPEG file
+channel (``op.jpeg_file_roundtrip``, 4:2:0 and 4:4:4) and ``op.pixel_attack`` with noise and with salt and pepper (draws made once,
+outside the timed window), written to ``--file_out``.
 
-    python tools/bench_attack.py [--out profiles/attack_jpeg.txt] [--spatial_out profiles/attack_spatial.txt] [--batch 32] [--size 256]
-        [--quality 75] [--reps 20]
+    python tools/bench_attack.py [--out profiles/attack_jpeg.txt] [--spatial_out profiles/attack_spatial.txt]
+        [--file_out profiles/attack_file_pixel.txt] [--batch 32] [--size 256] [--quality 75] [--reps 20]
 """
 import argparse
 import os
@@ -59,15 +61,9 @@ def window_ms(fn, xs, launches):
     return a.elapsed_time(b) / launches
 
 
-def spatial(xs, args):
-    """Per-call times of the spatial attacks through their ops, and the bytes a call must move over the measured HBM copy rate."""
-    from ideas_amd.op import gaussian_blur_u8, median_u8, resize_u8
+def timed_ops(title, variants, xs, args):
+    """Per-call times of ``variants`` (name, fn, launches, bytes moved) through their ops, and the bytes over the measured HBM copy rate."""
     b, r = args.batch, args.size
-    n = b * 3 * r * r
-    half = (max(1, r // 2), max(1, r // 2))
-    variants = (("scale:0.5", lambda x: resize_u8(resize_u8(x, half)[0], (r, r)), 2, n * (1 + 0.25 * 5) + n * (0.25 + 5)),
-                ("gblur:1", lambda x: gaussian_blur_u8(x, 1.0), 1, n * 6), ("gblur:4", lambda x: gaussian_blur_u8(x, 4.0), 1, n * 6),
-                ("median:3", lambda x: median_u8(x, 3), 1, n * 6), ("median:5", lambda x: median_u8(x, 5), 1, n * 6))
     for _ in range(args.warmup):
         for _, fn, _, _ in variants:
             window_ms(fn, xs, args.launches)
@@ -76,14 +72,61 @@ def spatial(xs, args):
     for _ in range(args.reps):
         for name, fn, _, _ in variants:
             ts[name].append(window_ms(fn, xs, args.launches))
-    lines = ["spatial attacks on the container, (%d, %d, %d, 3) uint8 with the received image, through the ops (output allocation included); "
+    lines = ["%s on the container, (%d, %d, %d, %d) uint8 with the received image, through the ops (output allocation included); "
              "per-call ms over windows of %d calls rotating over %d inputs, median of %d alternating windows [min .. max]; bytes = input, "
-             "output and received image of every launch" % (b, r, r, args.launches, args.sets, args.reps)]
+             "output and received image of every launch" % (title, b, r, r, xs[0].shape[3], args.launches, args.sets, args.reps)]
     for name, _, launches, moved in variants:
         v = ts[name]
         t = statistics.median(v)
-        lines.append("%-9s %8.4f  [%8.4f .. %8.4f]  %d launch(es), %.1f MB -> %.2f TB/s = %.0f %% of the measured HBM copy rate"
+        lines.append("%-13s %9.5f  [%9.5f .. %9.5f]  %d launch(es), %.1f MB -> %.2f TB/s = %.0f %% of the measured HBM copy rate"
                      % (name, t, min(v), max(v), launches, moved / 1e6, moved / (t * 1e-3) / 1e12, 100 * moved / (t * 1e-3) / HBM_MEASURED))
+    return lines
+
+
+def spatial(xs, args):
+    from ideas_amd.op import gaussian_blur_u8, median_u8, resize_u8
+    b, r = args.batch, args.size
+    n = b * 3 * r * r
+    half = (max(1, r // 2), max(1, r // 2))
+    variants = (("scale:0.5", lambda x: resize_u8(resize_u8(x, half)[0], (r, r)), 2, n * (1 + 0.25 * 5) + n * (0.25 + 5)),
+                ("gblur:1", lambda x: gaussian_blur_u8(x, 1.0), 1, n * 6), ("gblur:4", lambda x: gaussian_blur_u8(x, 4.0), 1, n * 6),
+                ("median:3", lambda x: median_u8(x, 3), 1, n * 6), ("median:5", lambda x: median_u8(x, 5), 1, n * 6))
+    return timed_ops("spatial attacks", variants, xs, args)
+
+
+def behind(x):
+    """a copy of ``x`` that starts one byte behind an aligned address: every kernel takes its byte path"""
+    buf = torch.empty(x.numel() + 1, device=x.device, dtype=x.dtype)
+    v = buf[1:].view(x.shape)
+    v.copy_(x)
+    return v
+
+
+def file_and_pixel(xs, args):
+    """The JPEG file channel (4:2:0: two launches and the half-resolution chroma workspace, written and read) and the pixel attack
+    (noise: 4 more bytes a byte read; salt and pepper: 4 a pixel); then the instantiations that the vector path at C = 3 does not
+    reach: the byte path (inputs one byte behind an aligned address), C = 1, and both."""
+    from ideas_amd.op import jpeg_file_roundtrip, jpeg_roundtrip, pixel_attack
+    b, r, q = args.batch, args.size, args.quality
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    noise = torch.randn(b, r, r, 3, device="cuda", generator=gen)
+    u = torch.rand(b, r, r, device="cuda", generator=gen)
+
+    def variants(c, first):
+        n = b * c * r * r
+        nz = noise[..., :c].contiguous()
+        v = (("jpegfile:444", lambda x: jpeg_file_roundtrip(x, q, "4:4:4"), 1, n * 6),
+             ("pixel:noise", lambda x: pixel_attack(x, sigma=8.0, noise=nz), 1, n * 10),
+             ("pixel:sp", lambda x: pixel_attack(x, sp=0.05, u=u), 1, n * 6 + 4 * (n // c)))
+        if c == 3:
+            v = (("jpegfile:420", lambda x: jpeg_file_roundtrip(x, q, "4:2:0"), 2, n * 6 + n + 2 * (n // 6)),) + v
+        return v if first else (("jpeg", lambda x: jpeg_roundtrip(x, q), 1, n * 6),) + v
+
+    title = "JPEG file channel (quality %d) and pixel attacks" % q
+    lines = timed_ops(title, variants(3, True), xs, args)
+    x1 = [x[..., :1].contiguous() for x in xs]
+    for what, c, inputs in (("byte path", 3, [behind(x) for x in xs]), ("C = 1", 1, x1), ("C = 1, byte path", 1, [behind(x) for x in x1])):
+        lines += [""] + timed_ops("JPEG round trip, %s, %s" % (title, what), variants(c, False), inputs, args)
     return lines
 
 
@@ -91,6 +134,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attack_jpeg.txt"))
     ap.add_argument("--spatial_out", default=os.path.join(ROOT, "profiles", "attack_spatial.txt"))
+    ap.add_argument("--file_out", default=os.path.join(ROOT, "profiles", "attack_file_pixel.txt"))
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=75)
@@ -144,7 +188,7 @@ def main():
              % (q, b, r, r, args.launches, args.sets, args.sets * n / 2 ** 20, args.reps)]
     for name, _ in variants:
         v = ts[name]
-        lines.append("%-9s %8.4f  [%8.4f .. %8.4f]" % (name, statistics.median(v), min(v), max(v)))
+        lines.append("%-9s %9.5f  [%9.5f .. %9.5f]" % (name, statistics.median(v), min(v), max(v)))
     t = statistics.median(ts["kernel"]) * 1e-3
     lines.append("kernel: %d bytes moved (B*H*W*C*(1+1+4): bytes in, bytes out, the received image) -> %.2f TB/s = %.0f %% of the measured "
                  "HBM copy rate (6.29 TB/s; the window includes the launch gaps); the bytes alone, %d each way, are %.0f %% of that time"
@@ -163,6 +207,11 @@ def main():
     with open(args.spatial_out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("wrote", args.spatial_out)
+    lines = file_and_pixel(xs, args)
+    print("\n".join(lines), flush=True)
+    with open(args.file_out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", args.file_out)
 
 
 if __name__ == "__main__":

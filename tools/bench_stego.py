@@ -85,7 +85,7 @@ def main():
              % (b, r, r, args.launches, args.sets, args.sets * n * 4 / 2 ** 20, args.reps)]
     for name, _ in variants:
         v = ts[name]
-        lines.append("%-9s %8.4f  [%8.4f .. %8.4f]" % (name, statistics.median(v), min(v), max(v)))
+        lines.append("%-9s %9.5f  [%9.5f .. %9.5f]" % (name, statistics.median(v), min(v), max(v)))
     t = statistics.median(ts["kernel"]) * 1e-3
     lines.append("kernel: %d bytes moved (B*C*H*W*(4+1+4)) -> %.2f TB/s = %.0f %% of the measured HBM copy rate (6.29 TB/s), %.0f %% of the "
                  "8.0 TB/s spec peak (the window includes the launch gaps)"

@@ -2,7 +2,7 @@
 """Hide a file in synthesised images (the sender of IDEAS: payload bits -> secret tensor -> Gstru -> G -> 8-bit PNGs).
 
     python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32] [--ecc RATE]
-                   [--format png|jpeg] [--jpeg_quality 90] [--jpeg_subsampling 420|444]
+                   [--format png|jpeg] [--jpeg_quality 90] [--jpeg_subsampling 420|444] [--jpeg_encoder pillow|device]
 
 The payload is framed (4-byte length, CRC32, payload, random padding: ``ideas_amd.stego.frame``) into whole images of
 ``N * (image_size / 16)^2 * sigma`` bits each and written as ``DIR/000000.png``, ``DIR/000001.png``, ...  ``extract.py`` with the same
@@ -14,7 +14,10 @@ codeword of a punctured convolutional code, fewer payload bytes, and ``extract.p
 ``--format jpeg`` writes ``DIR/000000.jpg``, ... through Pillow with ``quality=--jpeg_quality`` and ``subsampling=2`` (4:2:0, the
 default) or ``0`` (``--jpeg_subsampling 444``), nothing else.  A JPEG file is a lossy channel: what ``extract.py`` reads out of it is
 ``op.jpeg_file_roundtrip`` of the container's bytes, and ``evaluate.py --attack jpegfile:Q`` (``jpegfile:Q:444``) gives the accuracy
-to expect behind it; use ``--ecc``.
+to expect behind it; use ``--ecc``.  ``--jpeg_encoder device`` writes the files of ``op.jpeg_file_encode`` instead: the entropy coder runs on
+the GPU, one copy a batch brings the finished files over, and Pillow is not in the loop.  They are the files Pillow writes, byte for
+byte (a one-channel container at ``420`` differs in one header byte, the sampling factors, which Pillow sets to 2x2 and the device
+leaves at 1x1; both decode alike).
 """
 import argparse
 import os
@@ -35,6 +38,8 @@ def main(argv=None):
     parser.add_argument("--format", choices=("png", "jpeg"), default="png", help="container files: lossless PNG or JPEG (a lossy channel)")
     parser.add_argument("--jpeg_quality", type=int, default=90, metavar="Q", help="with --format jpeg: the quality, 1..100")
     parser.add_argument("--jpeg_subsampling", choices=("420", "444"), default="420", help="with --format jpeg: the chroma subsampling")
+    parser.add_argument("--jpeg_encoder", choices=("pillow", "device"), default="pillow",
+                        help="with --format jpeg: who writes the files, Pillow on the host or the entropy coder on the GPU (the same bytes)")
     opt = parser.parse_args(argv)
     if not 1 <= opt.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality: {opt.jpeg_quality} is outside 1..100")
@@ -44,9 +49,8 @@ def main(argv=None):
 
     if not torch.cuda.is_available():
         raise SystemExit("hide.py needs a GPU (ideas_amd has no CPU path)")
-    from PIL import Image
     from ideas_amd import stego
-    from ideas_amd.op import quantize_image
+    from ideas_amd.op import jpeg_file_encode, jpeg_files_to_host, quantize_image
 
     device = torch.device("cuda")
     models, args = stego.load_models(opt.ckpt, device)
@@ -68,10 +72,20 @@ def main(argv=None):
     gen = torch.Generator(device=device).manual_seed(opt.seed)
     os.makedirs(opt.out, exist_ok=True)
     print(f"capacity per image: {room}; payload {len(payload)} bytes -> {rows.shape[0]} image(s)")
+    on_device, written = opt.format == "jpeg" and opt.jpeg_encoder == "device", 0
+    if not on_device:
+        from PIL import Image
     for i0 in range(0, rows.shape[0], opt.batch):
         bits = rows[i0:i0 + opt.batch].to(device)
         images, _ = stego.hide(models, args, bits, opt.sigma, opt.delta, generator=gen)
         u8, _ = quantize_image(images, dequantize=False)
+        if on_device:
+            files = jpeg_files_to_host(*jpeg_file_encode(u8, opt.jpeg_quality, 2 if opt.jpeg_subsampling == "420" else 0))
+            for k, data in enumerate(files):
+                with open(os.path.join(opt.out, f"{i0 + k:06d}.jpg"), "wb") as f:
+                    f.write(data)
+                written += len(data)
+            continue
         for k, img in enumerate(u8.cpu().numpy()):
             im = Image.fromarray(img[..., 0] if img.shape[2] == 1 else img)
             if opt.format == "jpeg":
@@ -79,7 +93,7 @@ def main(argv=None):
                         subsampling=2 if opt.jpeg_subsampling == "420" else 0)
             else:
                 im.save(os.path.join(opt.out, f"{i0 + k:06d}.png"))
-    print(f"wrote {rows.shape[0]} image(s) to {opt.out}")
+    print(f"wrote {rows.shape[0]} image(s) to {opt.out}" + (f", {written} bytes" if on_device else ""))
 
 
 if __name__ == "__main__":

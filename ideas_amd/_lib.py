@@ -166,6 +166,9 @@ _PROTOS = {
     "ideas_pixel_attack": (C.c_int, [_P] * 5 + [C.c_int] * 4 + [C.c_float] * 4 + [_P]),
     "ideas_jpeg_file_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ideas_jpeg_file_roundtrip": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [_P]),
+    "ideas_jpeg_file_max_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ideas_jpeg_file_encode_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "ideas_jpeg_file_encode": (C.c_int, [_P, _P, C.c_longlong, _P, _P, _P] + [C.c_int] * 6 + [_P]),
     "ideas_resample_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "ideas_median_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_ecc_encode": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),

@@ -1,4 +1,4 @@
-"""Channel attacks on the 8-bit container, on the HIP kernels of csrc/attack.hip and csrc/attack_jpeg.hip: what a container suffers
+"""Channel attacks on the 8-bit container, on the HIP kernels of csrc/attack.hip, csrc/attack_jpeg.hip and csrc/jpeg_bytes.hip: what a container suffers
 between sender and receiver.
 
     jpeg_roundtrip(u8, quality)   a baseline-JPEG (4:4:4) encode and decode in one launch -- the model is stated step by step in
@@ -6,6 +6,10 @@ between sender and receiver.
     jpeg_file_roundtrip(u8, quality, subsampling)
                                   the JPEG FILE libjpeg / Pillow writes (integer DCT, 4:2:0 by default, triangle upsampler), exact
                                   to the byte -- stated in include/ideas_hip.h, restated by tests/jpegfile_ref.py
+    jpeg_file_encode(u8, quality, subsampling)
+                                  that FILE itself, written on the device (csrc/jpeg_bytes.hip): Pillow's ``Image.save`` bytes --
+                                  stated in include/ideas_hip.h, restated by tests/jpegbytes_ref.py; ``jpeg_files_to_host`` hands the
+                                  files over as ``bytes``
     pixel_attack(u8, ...)         intensity (gain, offset), additive Gaussian noise (sigma) and salt and pepper (sp) in one launch
 
 All take and return the uint8 ``[B, H, W, C]`` bytes of ``quantize_image`` (C = 1 or 3) together with ``y``, float32 ``[B, C, H, W]``
@@ -14,7 +18,7 @@ branch); forward-only.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -53,6 +57,17 @@ def jpeg_roundtrip(u8: torch.Tensor, quality: int, return_coef: bool = False):
 _SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2, 0: 0, 2: 2}
 
 
+def _file_args(u8: torch.Tensor, quality, subsampling, what: str) -> Tuple[torch.Tensor, int]:
+    """The validation ``jpeg_file_roundtrip`` and ``jpeg_file_encode`` share -> (the contiguous bytes, the subsampling code)."""
+    u8 = _bytes(u8, what)
+    if int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise RuntimeError(f"{what}: quality must be an integer in 1..100, got {quality!r}")
+    sub = _SUBSAMPLING.get(subsampling) if isinstance(subsampling, (str, int)) and not isinstance(subsampling, bool) else None
+    if sub is None:
+        raise RuntimeError(f"{what}: subsampling must be '4:4:4', '4:2:0', 0 or 2, got {subsampling!r}")
+    return u8, sub
+
+
 def jpeg_file_roundtrip(u8: torch.Tensor, quality: int, subsampling="4:2:0", return_coef: bool = False):
     """``u8`` through the JPEG FILE libjpeg / libjpeg-turbo writes at ``quality`` (1..100) with its defaults -- what Pillow's
     ``Image.save(f, "JPEG", quality=quality, subsampling=...)`` writes and ``Image.open`` reads back, byte for byte: the integer DCT,
@@ -60,12 +75,7 @@ def jpeg_file_roundtrip(u8: torch.Tensor, quality: int, subsampling="4:2:0", ret
     ``(u8, y, coef_y, coef_c)`` with ``return_coef``: the quantised coefficients int16 ``[B, ceil(H/8), ceil(W/8), 64]`` and
     ``[B, 2, cbh, cbw, 64]`` (Cb, Cr; the luma grid at 4:4:4, ``ceil(ceil(H/2)/8) x ceil(ceil(W/2)/8)`` at 4:2:0; ``None`` for
     C = 1) at index ``8 u + v``.  One launch, two at 4:2:0 with C = 3 (the workspace is allocated here)."""
-    u8 = _bytes(u8, "jpeg_file_roundtrip")
-    if int(quality) != quality or not 1 <= int(quality) <= 100:
-        raise RuntimeError(f"jpeg_file_roundtrip: quality must be an integer in 1..100, got {quality!r}")
-    sub = _SUBSAMPLING.get(subsampling) if isinstance(subsampling, (str, int)) and not isinstance(subsampling, bool) else None
-    if sub is None:
-        raise RuntimeError(f"jpeg_file_roundtrip: subsampling must be '4:4:4', '4:2:0', 0 or 2, got {subsampling!r}")
+    u8, sub = _file_args(u8, quality, subsampling, "jpeg_file_roundtrip")
     b, h, w, c = u8.shape
     out, y = _outputs(u8)
     coef_y = coef_c = None
@@ -83,6 +93,46 @@ def jpeg_file_roundtrip(u8: torch.Tensor, quality: int, subsampling="4:2:0", ret
                                            b, c, h, w, int(quality), sub, _lib.stream_ptr())
         _lib.check(rc, "ideas_jpeg_file_roundtrip")
     return (out, y, coef_y, coef_c) if return_coef else (out, y)
+
+
+def jpeg_file_encode(u8: torch.Tensor, quality: int, subsampling="4:2:0", return_decoded: bool = False):
+    """``u8`` as JPEG FILES, written on the device: the bytes of Pillow's ``Image.save(f, "JPEG", quality=quality, subsampling=...)``
+    (a baseline file, the standard Huffman tables) -> ``(files, nbytes)``: uint8 ``[B, max_bytes]`` and int32 ``[B]``, file ``b`` being
+    ``files[b, :nbytes[b]]`` (``jpeg_files_to_host`` cuts them out), or ``(files, nbytes, out, y)`` with ``return_decoded``: what
+    ``jpeg_file_roundtrip`` returns, the image a receiver decodes from those files.  Arguments as ``jpeg_file_roundtrip``.  The round
+    trip's launches, then four more and a memset (the workspace is allocated here)."""
+    u8, sub = _file_args(u8, quality, subsampling, "jpeg_file_encode")
+    b, h, w, c = u8.shape
+    out, y, coef_y, coef_c = jpeg_file_roundtrip(u8, quality, sub, return_coef=True)
+    lib = _lib.load()
+    stride = int(lib.ideas_jpeg_file_max_bytes(c, h, w, sub))
+    if stride == 0:
+        raise RuntimeError(f"jpeg_file_encode: a JPEG file holds at most 65535 x 65535 pixels and 2^31 - 1 bytes, got {h} x {w}")
+    files = torch.empty((b, stride), device=u8.device, dtype=torch.uint8)
+    nbytes = torch.empty((b,), device=u8.device, dtype=torch.int32)
+    if u8.numel():
+        work = torch.empty((int(lib.ideas_jpeg_file_encode_workspace_bytes(b, c, h, w, sub)),), device=u8.device, dtype=torch.uint8)
+        rc = lib.ideas_jpeg_file_encode(_lib.ptr(files), _lib.ptr(nbytes), stride, _lib.ptr(coef_y), _lib.ptr(coef_c), _lib.ptr(work),
+                                        b, c, h, w, int(quality), sub, _lib.stream_ptr())
+        _lib.check(rc, "ideas_jpeg_file_encode")
+    return (files, nbytes, out, y) if return_decoded else (files, nbytes)
+
+
+def jpeg_files_to_host(files: torch.Tensor, nbytes: torch.Tensor) -> List[bytes]:
+    """``jpeg_file_encode``'s ``(files, nbytes)`` as a list of ``bytes``, one file each.  ONE device-to-host copy and no
+    synchronisation in front of it: the lengths ride in front of the rows, whole (the longest file is not known on the host)."""
+    _lib.require_cuda(files, nbytes)
+    if files.dtype != torch.uint8 or files.dim() != 2 or nbytes.dtype != torch.int32 or tuple(nbytes.shape) != (files.shape[0],):
+        raise RuntimeError(f"jpeg_files_to_host expects uint8 [B, max_bytes] and int32 [B], got {files.dtype} {tuple(files.shape)} and "
+                           f"{nbytes.dtype} {tuple(nbytes.shape)}")
+    if files.shape[0] == 0:
+        return []
+    host = torch.cat((nbytes.view(torch.uint8).view(-1, 4), files), dim=1).cpu().numpy()
+    lengths = host[:, :4].copy().view("<i4")[:, 0]
+    if (lengths < 0).any():
+        raise RuntimeError(f"jpeg_files_to_host: image(s) {[int(i) for i in (lengths < 0).nonzero()[0]]} hold a coefficient that has no "
+                           "Huffman code")
+    return [host[i, 4:4 + int(n)].tobytes() for i, n in enumerate(lengths)]
 
 
 def _draw(fn, shape, generator: Optional[torch.Generator], device) -> torch.Tensor:

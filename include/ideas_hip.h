@@ -738,6 +738,56 @@ int ideas_jpeg_file_roundtrip(void* out_u8, float* y, short* coef_y, short* coef
                               int H, int W, int quality, int subsampling, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The JPEG file, written, csrc/jpeg_bytes.hip: the lossless last step behind ideas_jpeg_file_roundtrip -- from its quantised
+ * coefficients coef_y and coef_c to the FILE that libjpeg / libjpeg-turbo writes with its defaults, i.e. the bytes of Pillow's
+ * Image.save(f, "JPEG", quality=Q, subsampling=0|2): a baseline file with the standard Huffman tables, not optimised, no restart
+ * markers.  Defined to the byte: tests/jpegbytes_ref.py restates it in Python and tests/test_jpeg_bytes.py holds that restatement to
+ * Pillow's own files.  The file:
+ *   Header (328 bytes for C = 1, 623 for C = 3):
+ *     1. FFD8.
+ *     2. FFE0 0010 'JFIF\0' 01 01 00 0001 0001 00 00.
+ *     3. One DQT segment per table, FFDB 0043 0i and 64 bytes: table i of the quality rule (step 2 of the round trip) in zigzag
+ *        order.  i = 0 luma; i = 1 chroma, only with C = 3.
+ *     4. FFC0, length 8 + 3 C, 08, H and W as two bytes each, C, then per component id, sampling, table: 1, 22 at 4:2:0 with C = 3
+ *        and 11 otherwise, 0;  2, 11, 1;  3, 11, 1.  (C = 1 writes 11 whatever `subsampling` says.  Pillow copies a subsampling of 2
+ *        into this one byte of a one-channel file too; the scan, and what a decoder reads, are the same.)
+ *     5. One DHT segment per Huffman table in the order DC0 (00), AC0 (10), DC1 (01), AC1 (11), C = 1 the first two only: FFC4,
+ *        length 001F (DC) or 00B5 (AC), the id, the 16 counts and the symbols of ISO/IEC 10918-1 Annex K.3 - K.6.
+ *     6. FFDA, length 6 + 2 C, C, the pairs (1, 00), (2, 11), (3, 11), then 00 3F 00.
+ *   Scan order: MCUs in raster order; an MCU is 8 hs x 8 hs pixels, hs = 2 for C = 3 at 4:2:0 and 1 otherwise; the MCU grid is
+ *     ceil(H / 8 hs) x ceil(W / 8 hs), which is also the chroma block grid of coef_c.  Inside an MCU the hs x hs luma blocks in raster
+ *     order, then Cb, then Cr.
+ *   Dummy luma blocks at 4:2:0: the luma grid of coef_y, ceil(H/8) x ceil(W/8), can be one block short of the MCUs on the right and at
+ *     the bottom (wherever ceil(W/8) or ceil(H/8) is odd).  A missing block is coded with all AC zero and the DC of the luma block
+ *     before it in the same MCU: a right-edge dummy copies the block on its left; in a dummy bottom row block (1,0) copies (0,1), which
+ *     may itself be a dummy, and (1,1) copies (1,0).
+ *   Block coding: DC: d = DC - pred, pred the DC of the previous block of the same component in scan order, dummies included, 0 at
+ *     the start.  nb = the bit length of |d| (0..11); the code of nb, then the low nb bits of d (d >= 0) or of d - 1 (d < 0).  AC in
+ *     zigzag order with r the run of zeros since the last non-zero coefficient: ZRL (F0) while r > 15, then the symbol (r << 4) | nb,
+ *     nb = 1..10, and the bits as for DC.  EOB (00) if zeros trail; none when coefficient 63 is non-zero.
+ *   End: the last byte is padded with 1 bits; every FF byte of the scan, padding included, is followed by 00; then FFD9.
+ *   Size: a block is at most 22 + 63 * 26 = 1660 bits, 208 bytes, twice that stuffed:
+ *     ideas_jpeg_file_max_bytes = header + 416 * blocks + 3, blocks counting every block of the scan, dummies included; 0 for
+ *     arguments the encoder refuses (C other than 1 or 3, H or W outside 1..65535, subsampling other than 0 or 2, a bound or a
+ *     launch beyond 2^31 - 1).
+ * files: uint8 [B][row_stride], row_stride >= the bound; nbytes[b] = the length of file b, the bytes behind it unspecified.  An image
+ * with a coefficient that has no code (|AC| > 1023, a DC difference beyond +-2047: the entry point takes any int16) gets
+ * nbytes[b] = -1 and unspecified bytes inside its row; the other images of the batch are not affected.  workspace:
+ * ideas_jpeg_file_encode_workspace_bytes (0 for refused arguments), any alignment, any contents: what needs zeros is cleared on the
+ * stream inside the call.  Nothing is written outside files, nbytes and workspace.  Bit and byte offsets inside an image are 64-bit.
+ * Four launches behind one memset: one thread a block counts its bits; one workgroup an image turns the counts into offsets; one
+ * thread a block writes its bits there (its first and last 32-bit word, shared with the neighbours, by atomicOr: the result does not
+ * depend on the order); one workgroup an image writes the header, stuffs and copies the scan and writes FFD9 and the length.  Every grid
+ * is exact (no capped grid-stride loop).
+ * IDEAS_E_NULL: files, nbytes, coef_y or workspace is NULL, or coef_c with C = 3.  IDEAS_E_SHAPE: B, H or W <= 0, H or W > 65535, C
+ * other than 1 or 3, row_stride below the bound, a size the size query answers with 0.  IDEAS_E_UNSUPPORTED: quality outside 1..100,
+ * subsampling other than 0 or 2.  Every check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+size_t ideas_jpeg_file_max_bytes(int C, int H, int W, int subsampling);
+size_t ideas_jpeg_file_encode_workspace_bytes(int B, int C, int H, int W, int subsampling);
+int ideas_jpeg_file_encode(void* files, int* nbytes, long long row_stride, const short* coef_y, const short* coef_c, void* workspace,
+                           int B, int C, int H, int W, int quality, int subsampling, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Spatial channel attacks on the 8-bit container, csrc/attack_spatial.hip: rescaling, Gaussian filtering and median filtering, what
  * a messenger or an image host does to a picture before it re-encodes it.  Integer arithmetic throughout: every result is defined
  * to the byte (tests/spatial_ref.py restates it in numpy; the resize is Pillow's Image.resize(size, Image.BILINEAR) on 8-bit

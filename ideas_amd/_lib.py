@@ -106,6 +106,7 @@ _PROTOS = {
     "ideas_b3_split_weights_strided": (C.c_int, [_P, _P] + [C.c_int] * 4 + [C.c_int64] * 4 + [_P]),
     "ideas_bf16_conv_supported": (C.c_int, [C.POINTER(ConvParams), C.c_int]),
     "ideas_bf16_wgrad_supported": (C.c_int, [C.POINTER(ConvParams), C.c_int]),
+    "ideas_bf16_wgrad3_supported": (C.c_int, [C.POINTER(ConvParams)]),
     "ideas_bf16_direct_supported": (C.c_int, [C.POINTER(ConvParams)]),
     "ideas_bf16_pack_weights": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ideas_bf16_pack_weights_strided": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [C.c_int64] * 4 + [_P]),

@@ -856,6 +856,20 @@ int ideas_bf16_fwd_multi(int n, void* y, const void* x, const void* const* wpack
     });
 }
 
+// Which forward kernel the two entries above choose for (*p, per_image), for tests and A/B scripts (a diagnostic beside the ABI of
+// include/ideas_hip.h, not bound by ideas_amd/_lib.py): out = {rows, channels, waves} of the generic tile bf16_fwd_tile hands out
+// (256 x 128 on 8 waves; 128 x 128, 128 x 64, 128 x 32 on 4) and out[3] = the patch width of the LDS-image kernel where ideas_bf16_fwd
+// gives it the launch before the ladder is asked (bf16_img_tp; 0: the tile of out[0..2] runs).  ideas_bf16_fwd_multi has no image
+// kernel: out[3] does not concern it.  The flat 1x1 decision (ideas_bf16_pw_ok) reads the pointers and is not answered here.
+extern "C" int ideas_bf16_fwd_choice(const ideas_conv_params* p, int per_image, int* out) {
+    if (!p || !out) return IDEAS_E_NULL;
+    out[3] = bf16_img_tp(p);
+    return bf16_fwd_tile(p, per_image, [&](auto t) {
+        out[0] = t.BM; out[1] = t.BN; out[2] = t.WM * t.WN;
+        return (int)IDEAS_OK;
+    });
+}
+
 // Tile-shape A/B for tools/bench_igemm.py --cfg (not part of the declared ABI; the production dispatch is ideas_bf16_fwd)
 extern "C" int ideas_tune_bf16_fwd(int cfg, void* y, const void* x, const void* wpack, int per_image, const float* out_scale,
                                    const float* bias, const void* resid, const ideas_conv_params* p, void* stream_) {
@@ -1082,7 +1096,16 @@ static bool bf16_wgrad3_ok(const ideas_conv_params* p) {
     if (p->offx > 0 || p->offx < -2 || p->offy > 0 || p->offy < -2) return false;
     if (p->reflect && (p->IH < 2 || p->IW < 2)) return false;
     // (small layers: the generic kernel's fewer, fatter splits win -- E.2.conv1, 64 -> 128 at 128x128, B = 32: 549 vs 459 TFLOP/s)
-    return (int64_t)p->B * p->OH * p->OW * p->Cin * p->Cout >= 6000000000LL;
+    // IDEAS_BF16_WGRAD3_MIN_WORK in the environment moves the floor (0: every shape the geometry admits -- tests at small shapes)
+    const char* e = getenv("IDEAS_BF16_WGRAD3_MIN_WORK");
+    const int64_t min_work = e ? atoll(e) : 6000000000LL;
+    return (int64_t)p->B * p->OH * p->OW * p->Cin * p->Cout >= min_work;
+}
+
+// 1 exactly when ideas_conv_wgrad(IDEAS_BF16) launches conv_bf16_wgrad3_kernel for *p now: the entry's own shape rule, the geometry,
+// IDEAS_BF16_WGRAD3 and the work floor.  ideas_bf16_wgrad asks this function, so the query and the launch cannot disagree.
+extern "C" int ideas_bf16_wgrad3_supported(const ideas_conv_params* p) {
+    return p && ideas_bf16_wgrad_supported(p, 0) && bf16_wgrad3_ok(p) ? 1 : 0;
 }
 
 // split-K plan of the tap-fused kernel: a rule of its own -- PARTS of the rows of one image (a block's range lies inside one image):
@@ -1113,7 +1136,7 @@ int launch_bf16_wgrad3(float* gw, const void* gy, const void* x, const float* in
 
 int ideas_bf16_wgrad(float* gw, const void* gy, const void* x, const float* in_scale, const float* out_scale,
                      const ideas_conv_params* p, hipStream_t stream) {
-    if (bf16_wgrad3_ok(p)) return launch_bf16_wgrad3(gw, gy, x, in_scale, out_scale, p, stream);    // 3x3 / s1: tap-fused, rolling window
+    if (ideas_bf16_wgrad3_supported(p)) return launch_bf16_wgrad3(gw, gy, x, in_scale, out_scale, p, stream);    // 3x3 / s1: tap-fused, rolling window
     // (an 8-wave 256 x 128 tile, the winner of the forward family, measured 22 % SLOWER here: half the blocks for the split-K)
     return ideas_wgrad_tile(p, [&](auto t) { return launch_bf16_wgrad_cfg<decltype(t)>(gw, gy, x, in_scale, out_scale, p, stream); });
 }

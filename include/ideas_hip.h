@@ -15,8 +15,11 @@
  *     besides its arguments is a handful of A/B measurement switches in the process environment, looked up PER CALL (nothing is
  *     cached in the library): IDEAS_B3_WINO2D, IDEAS_B3_TPHASE, IDEAS_B3_WGRAD3, IDEAS_B3_WGRAD3_S2, IDEAS_S2FIR_CFG,
  *     IDEAS_BF16_IMG, IDEAS_BF16_WGRAD3, IDEAS_B3_PW, IDEAS_B3_PW_WGRAD, IDEAS_BF16_PW, IDEAS_B3_WINO_EPI, IDEAS_S2IMG_MIN_BLOCKS,
- *     IDEAS_B3_WINO_N256 -- each "0" selects the older kernel of its family, unset = the default dispatch; the *_MIN_BLOCKS
- *     variable and IDEAS_B3_WINO_N256 also take a number.
+ *     IDEAS_B3_WINO_N256, IDEAS_BF16_WGRAD3_MIN_WORK -- each "0" selects the older kernel of its family, unset = the default
+ *     dispatch; the *_MIN_BLOCKS variable, IDEAS_B3_WINO_N256 and IDEAS_BF16_WGRAD3_MIN_WORK also take a number.
+ *     (IDEAS_BF16_WGRAD3_MIN_WORK: the least B * OH * OW * Cin * Cout at which ideas_conv_wgrad(IDEAS_BF16) gives a 3x3 / stride-1
+ *     layer to the tap-fused kernel; unset = 6000000000; "0" here admits every shape the kernel's geometry covers, so that tests
+ *     reach it at small shapes.  ideas_bf16_wgrad3_supported answers for a shape under the current environment.)
  *     (IDEAS_B3_WINO_N256: "0" keeps the 64 x 128 tile of the row-sharing Winograd kernel where Cout % 256 == 0; a positive number
  *     n replaces the default tile-count rule by "at least n tiles of 64 x 256" (1: wherever Cout allows).  A diagnostic query beside this ABI, defined next to the
  *     dispatch in csrc/conv_b3_wino.hip, tells tests and A/B scripts which tile a forward of a given shape takes.)
@@ -236,6 +239,15 @@ int ideas_b3_wino_split_weights(void* planes, const void* w, int N, int C, int64
  *                               to ideas_conv_igemm (it selects the per-sample packs; the scale itself is already applied). */
 int ideas_bf16_conv_supported(const ideas_conv_params* p, int scaled);
 int ideas_bf16_wgrad_supported(const ideas_conv_params* p, int scaled);
+int ideas_bf16_wgrad3_supported(const ideas_conv_params* p);   /* 1 exactly when ideas_conv_wgrad(IDEAS_BF16) launches the tap-fused 3x3
+                                                                   kernel for *p under the current environment (3x3, unit stride and
+                                                                   dilation, offsets -2 .. 0, OW % 32 == 0, OH >= 8, Cin % 64 == 0,
+                                                                   Cout % 64 == 0, IDEAS_BF16_WGRAD3 not "0", B * OH * OW * Cin * Cout
+                                                                   >= IDEAS_BF16_WGRAD3_MIN_WORK); the launcher asks this function.
+                                                                   Informational; additive within ABI 4 */
+/* (A diagnostic query beside this ABI, defined next to the dispatch in csrc/conv_bf16.hip, tells tests and A/B scripts which forward
+ * tile -- 256 x 128 on 8 waves, 128 x 128, 128 x 64 or 128 x 32 -- a launch of a given shape takes, and whether the LDS-image kernel
+ * takes it first.) */
 int ideas_bf16_pack_weights(void* pack, const void* wmat, const float* in_scale, int B, int Cout, int K, int Cin, void* stream);
 /* ideas_bf16_pack_weights reading the matrix through strides (see ideas_b3_split_weights_strided). */
 int ideas_bf16_pack_weights_strided(void* pack, const float* w, const float* in_scale, int B, int Cout, int TY, int TX, int Cin,

@@ -59,6 +59,61 @@ def bf16_mode():
         yield
 
 
+# ------------------------------------------------------------------------- which forward kernel a launch takes: the library's answer
+TILE_8WAVE = (256, 128, 8)       # rows, channels, waves of bf16_fwd_tile's first rung (csrc/conv_bf16.hip)
+
+
+def fwd_choice(p, per_image):
+    """ideas_bf16_fwd_choice (the diagnostic beside the ABI, csrc/conv_bf16.hip) for (*p, per_image): ((rows, channels, waves) of the
+    generic tile bf16_fwd_tile hands out, patch width of the LDS-image kernel where that one takes a single launch first or 0)."""
+    import ctypes as C
+    from ideas_amd import _lib
+    fn = C.CDLL(_lib.LIB_PATH).ideas_bf16_fwd_choice
+    fn.argtypes, fn.restype = [C.POINTER(_lib.ConvParams), C.c_int, C.POINTER(C.c_int)], C.c_int
+    out = (C.c_int * 4)()
+    assert fn(C.byref(p), int(per_image), out) == 0
+    return tuple(out[:3]), out[3]
+
+
+@pytest.fixture()
+def fwd_launches(monkeypatch):
+    """Every bf16 forward-family launch op/conv.py enqueues while the test runs, as (kind, params, per_image, tile, img_tp): kind
+    "single" = ideas_conv_igemm (launch_fwd), "multi" = ideas_conv_igemm_multi (launch_multi: its first, heaviest launch, the one
+    ideas_bf16_fwd_multi takes the tile from); tile / img_tp = fwd_choice's answer at the moment of the launch."""
+    import ideas_amd.op.conv as CV
+    log = []
+    fwd0, multi0 = CV.launch_fwd, CV.launch_multi
+
+    def launch_fwd(y, x, L, gain, in_scale=None, *a, **k):
+        if x.dtype == BF:
+            p = CV._params(L, gain)
+            log.append(("single", p, int(in_scale is not None)) + fwd_choice(p, in_scale is not None))
+        return fwd0(y, x, L, gain, in_scale, *a, **k)
+
+    def launch_multi(y, x, launches, gain, in_scale=None, out_scale=None):
+        done = multi0(y, x, launches, gain, in_scale, out_scale)
+        if done and x.dtype == BF:
+            p = CV._params(max(launches, key=lambda L: L.TY * L.TX * L.OH * L.OW), gain)
+            log.append(("multi", p, int(in_scale is not None)) + fwd_choice(p, in_scale is not None))
+        return done
+    monkeypatch.setattr(CV, "launch_fwd", launch_fwd)
+    monkeypatch.setattr(CV, "launch_multi", launch_multi)
+    return log
+
+
+def assert_8wave(log, kind, per_image=0):
+    """Among the recorded launches, the ones of `kind` with >= 256 output channels -- the launches the case is there for -- exist and
+    ran the 8-wave 256 x 128 tile: not the LDS-image kernel, not the flat 1x1 kernel (whose rule reads the pointers: restated by
+    test_conv_epilogue_pinned_gpu.py), not a 4-wave tile."""
+    from test_conv_epilogue_pinned_gpu import _bf16_pw_shape
+    sel = [e for e in log if e[0] == kind and e[1].Cout >= 256 and e[2] == per_image]
+    assert sel, (kind, [(e[0], e[1].Cout, e[2]) for e in log])
+    for _, p, pi, tile, tp in sel:
+        assert tile == TILE_8WAVE, (kind, p.Cout, p.B, p.OH, p.OW, tile)
+        if kind == "single":
+            assert tp == 0 and not (_bf16_pw_shape(p) and not pi), (p.Cout, p.OH, p.OW, tp)
+
+
 # ------------------------------------------------------------------------------------------------- convolutions
 CONV_CASES = [
     # B, Cin, Cout, k, stride, pad, reflect, H, W            (Cin % 32 == 0: MFMA kernel; others: direct / f32 fallback)
@@ -74,16 +129,39 @@ CONV_CASES = [
     (3, 32, 128, 3, 1, 1, False, 8, 96),
     # ... mirror padding (forward only), the 64-channel N tile, 16 x 16 patches over a larger image
     (2, 64, 128, 3, 1, 1, True, 8, 64), (2, 32, 64, 3, 1, 1, True, 16, 32), (2, 64, 64, 3, 1, 1, False, 4, 64), (2, 32, 96, 3, 1, 1, False, 32, 48),
-    # conv_bf16_wgrad3_kernel (tap-fused weight gradient: Cin, Cout % 64 == 0, W % 32 == 0): three strips, several parts per image,
-    # a 2 x 2 grid of channel tiles (the cases (2, 64, 128, .., 8, 64) above -- plain and mirror-padded -- take it as well)
+    # the geometry of the tap-fused weight gradient (Cin, Cout % 64 == 0, W % 32 == 0): three strips, a 2 x 2 grid of channel tiles.
+    # Here -- as for (2, 64, 128, .., 8, 64) above, plain and mirror-padded -- the weight gradient is the GENERIC kernel's: the
+    # dispatch keeps layers under 6e9 products off the tap-fused one.  WGRAD3_OP_CASES runs these again with the floor at 0.
     (3, 64, 64, 3, 1, 1, False, 40, 96), (2, 128, 128, 3, 1, 1, False, 16, 32),
     # many samples of <= 4x4 output pixels (K-steps of whole samples, csrc/conv_bf16.hip; test_tiny_spatial_weight_gradient_vs_f64)
     (300, 64, 96, 3, 1, 1, False, 2, 2), (80, 64, 64, 3, 2, 0, False, 9, 9),
 ]
+# The 8-wave 256 x 128 tile of the generic forward family (Cout >= 256 and >= 256 rows): case -> the launch that must take it
+# (asserted from the library's answer for the launch the op makes).  512 rows = two whole M tiles and two N tiles; 306 rows and 260
+# channels: the last M tile clamped, a third N tile of 4 channels whose weight pieces run past the pack; mirror padding (18 columns
+# keep it off the LDS-image kernel); a single tap with Cin outside the flat 1x1 kernel's 32 / 64 / 128; and a stride-2 layer whose
+# input gradient is four parity phases of 256 channels with 2 x 17 x 17 rows at most: conv_bf16_multi_kernel<4, 2, 2, 2, false>.
+CONV_8WAVE = {
+    (2, 32, 256, 3, 2, 0, False, 33, 33): "single", (1, 64, 260, 3, 2, 0, False, 35, 37): "single",
+    (1, 32, 256, 3, 1, 1, True, 17, 18): "single", (1, 256, 256, 1, 1, 0, False, 16, 17): "single",
+    (2, 256, 64, 3, 2, 0, False, 33, 33): "multi",
+}
+CONV_CASES += list(CONV_8WAVE)
+# the cases named above for conv_bf16_img_kernel -> the patch width the library reports for their forward launch
+CONV_IMG = {
+    (2, 64, 128, 3, 1, 1, False, 8, 64): 64, (1, 128, 200, 3, 1, 1, False, 4, 128): 64, (2, 96, 96, 3, 1, 1, False, 16, 32): 32,
+    (3, 32, 128, 3, 1, 1, False, 8, 96): 32, (2, 64, 128, 3, 1, 1, True, 8, 64): 64, (2, 32, 64, 3, 1, 1, True, 16, 32): 32,
+    (2, 64, 64, 3, 1, 1, False, 4, 64): 64, (2, 32, 96, 3, 1, 1, False, 32, 48): 16,
+}
+assert set(CONV_IMG) <= set(CONV_CASES)
+CONV_TWICE = CONV_CASES[-5:-3]      # forward run twice, bitwise equal: no atomics there, and a wrong counted wait is a race, not a bias
+# the shapes whose weight gradient is conv_bf16_wgrad3_kernel's once the floor is out of the way
+WGRAD3_OP_CASES = [(3, 64, 64, 3, 1, 1, False, 40, 96), (2, 128, 128, 3, 1, 1, False, 16, 32), (2, 64, 128, 3, 1, 1, False, 8, 64),
+                   (2, 64, 128, 3, 1, 1, True, 8, 64)]
 
 
-@pytest.mark.parametrize("case", CONV_CASES)
-def test_conv_bf16_vs_f64_on_rounded_operands(ops, bf16_mode, case):
+def conv_bf16_vs_f64(ops, case, log=None, wgrad3=False):
+    import ctypes as C
     B, ci, co, k, s, p, refl, H, W = case
     torch.manual_seed(sum(case[:6]) + H)
     x = bf(torch.randn(B, ci, H, W, dtype=torch.float64)).requires_grad_(True)
@@ -96,13 +174,41 @@ def test_conv_bf16_vs_f64_on_rounded_operands(ops, bf16_mode, case):
     gx, gw = torch.autograd.grad(y, (x, w), gy)
     xd = dev(x, dtype=BF).requires_grad_(True)
     wd = dev(w.float()).requires_grad_(True)             # exactly representable in bf16: no second rounding
+    if wgrad3:      # the library says that this weight gradient is the tap-fused kernel's
+        import ideas_amd.op.conv as CV
+        from ideas_amd import _lib
+        from ideas_amd.op.conv_plan import ConvGeom, plan_wgrad
+        pw = CV._params(plan_wgrad(x.shape, y.shape, ConvGeom(k, k, s, p, refl)), scale)
+        assert _lib.load().ideas_bf16_wgrad3_supported(C.byref(pw)) == 1, case
     yd = ops.conv2d(xd, wd, None, stride=s, padding=p, reflect=refl, gain=scale)
     assert yd.dtype == BF and tuple(yd.shape) == tuple(y.shape)
     close_bf16(yd, y, ("y", case))
+    if case in CONV_TWICE:
+        assert torch.equal(yd, ops.conv2d(xd, wd, None, stride=s, padding=p, reflect=refl, gain=scale)), ("y twice", case)
+    if CONV_8WAVE.get(case) == "single":
+        assert_8wave(log, "single")
+    if case in CONV_IMG and log is not None:
+        assert [e[4] for e in log if e[0] == "single"] == [CONV_IMG[case]], (case, [e[4] for e in log])
     gxd, gwd = torch.autograd.grad(yd, (xd, wd), dev(gy, dtype=BF))
+    if CONV_8WAVE.get(case) == "multi":
+        assert_8wave(log, "multi")
     assert gxd.dtype == BF and gwd.dtype == torch.float32
     close_bf16(gxd, gx, ("gx", case), roundings=3 if refl else 1)    # reflect: the padded gradient is rounded, then folded
     assert rel_err(gwd, gw) < 1e-3, ("gw", case, rel_err(gwd, gw))
+
+
+@pytest.mark.parametrize("case", CONV_CASES)
+def test_conv_bf16_vs_f64_on_rounded_operands(ops, bf16_mode, fwd_launches, case):
+    conv_bf16_vs_f64(ops, case, fwd_launches)
+
+
+@pytest.mark.parametrize("case", WGRAD3_OP_CASES)
+def test_conv_bf16_vs_f64_with_the_tap_fused_weight_gradient(ops, bf16_mode, monkeypatch, case):
+    """The op-level check again for the 3x3 / stride-1 shapes of CONV_CASES that conv_bf16_wgrad3_kernel covers, with the work floor
+    of its dispatch at 0 (IDEAS_BF16_WGRAD3_MIN_WORK): the weight gradient autograd gets is then that kernel's, which
+    ideas_bf16_wgrad3_supported confirms first.  Same bounds."""
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", "0")
+    conv_bf16_vs_f64(ops, case, wgrad3=True)
 
 
 PW_BF16_CASES = [
@@ -202,22 +308,117 @@ def test_tiny_spatial_weight_gradient_vs_f64(case):
         assert rel_err(got2, ref2) < 2e-5, (case, "in-kernel scales", rel_err(got2, ref2))
 
 
+WGRAD3_CASES = [
+    # ((B, Cin, Cout, OH, OW, pad, reflect, scaled), (parts per image, rows per part, strips) of ideas_bf16_wgrad3_plan); x is sized
+    # so that the 3x3 / stride-1 output is OH x OW.  The kernel does OH + 2 steps per part, unrolled over the six ring positions:
+    # the minimum height and all six exits of the step loop; one strip, one tile, one part
+    ((1, 64, 64, 8, 32, 1, False, False), (1, 8, 1)), ((1, 64, 64, 9, 32, 1, False, False), (1, 9, 1)),
+    ((1, 64, 64, 10, 32, 1, False, False), (1, 10, 1)), ((1, 64, 64, 11, 32, 1, False, False), (1, 11, 1)),
+    ((1, 64, 64, 12, 32, 1, False, False), (1, 12, 1)), ((1, 64, 64, 13, 32, 1, False, False), (1, 13, 1)),
+    # 2 x 2 channel tiles, two strips, two images (the img * IH / img * OH row bases)
+    ((2, 128, 128, 9, 64, 1, False, False), (1, 9, 2)),
+    # three parts of 33 rows, the last one 31; two parts of 33 and 32 rows
+    ((1, 64, 128, 97, 32, 1, False, False), (3, 33, 1)), ((1, 64, 64, 65, 32, 1, False, False), (2, 33, 1)),
+    # mirror padding at all four edges, three strips: the left edge in strip 0, the right edge (window column 33) in strip 2
+    ((2, 64, 64, 10, 96, 1, True, False), (1, 10, 3)),
+    # per-sample scales applied in the kernel: <SCALE, zero padding> and <SCALE, REFLECT>
+    ((3, 64, 128, 9, 32, 1, False, True), (1, 9, 1)), ((2, 64, 64, 9, 32, 1, True, True), (1, 9, 1)),
+    # offx = offy = 0 (input 10 x 34) and offx = offy = -2 (input 8 x 30)
+    ((1, 64, 64, 8, 32, 0, False, False), (1, 8, 1)), ((1, 64, 64, 10, 32, 2, False, False), (1, 10, 1)),
+]
+WGRAD3_GAIN = 0.37
+
+
+def wgrad3_launch(case):
+    """(geometry, x shape, gy shape, ideas_conv_params of the weight-gradient launch) of a WGRAD3_CASES row."""
+    import ideas_amd.op.conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom, plan_wgrad
+    B, ci, co, OH, OW, pad, refl, scaled = case
+    g = ConvGeom(3, 3, 1, pad, refl)
+    xs, gs = (B, ci, OH + 2 - 2 * pad, OW + 2 - 2 * pad), (B, co, OH, OW)
+    return g, xs, gs, CV._params(plan_wgrad(xs, gs, g), WGRAD3_GAIN)
+
+
+@pytest.mark.parametrize("case,plan", WGRAD3_CASES)
+def test_bf16_tap_fused_weight_gradient_vs_f64(case, plan, monkeypatch):
+    """conv_bf16_wgrad3_kernel at the smallest shapes that reach each of its paths (WGRAD3_CASES; the part structure each row names is
+    checked against the plan query in test_host_logic.py), where a wrong edge column or a wrong last row of a part is a first-order
+    error: against f64 on the same bf16-rounded operands, accumulated into a gradient prefilled with 0.5, within the bound of
+    test_tiny_spatial_weight_gradient_vs_f64 (f32 accumulation of exact bf16 products).  The work floor of the dispatch is at 0
+    (IDEAS_BF16_WGRAD3_MIN_WORK) and ideas_bf16_wgrad3_supported -- the function the launcher asks -- confirms the kernel; then
+    again with IDEAS_BF16_WGRAD3=0, where it says 0: the generic kernel is held to the same reference and bound.  Scaled rows are
+    large enough (> PRESCALE_MOD_PIX pixels) for the per-sample scales to reach the kernel, which applies them to its accumulators:
+    the reference is f64 on the unscaled rounded operands times the scales."""
+    import ctypes as C
+    import ideas_amd.op.conv as CV
+    from ideas_amd import _lib
+    B, ci, co, OH, OW, pad, refl, scaled = case
+    torch.manual_seed(sum(case[:6]))
+    g, xs, gs, p = wgrad3_launch(case)
+    x, gy = bf(torch.randn(*xs, dtype=torch.float64)), bf(torch.randn(*gs, dtype=torch.float64))
+    lin = (torch.rand(B, ci) + 0.5) if scaled else None
+    lout = (torch.rand(B, co) + 0.5) if scaled else None
+    w = torch.zeros(co, ci, 3, 3, dtype=torch.float64, requires_grad=True)
+    xin = x * lin.double()[:, :, None, None] if scaled else x
+    xin = F.pad(xin, [pad] * 4, mode="reflect") if refl else xin
+    ref, = torch.autograd.grad(F.conv2d(xin, w, padding=0 if refl else pad) * WGRAD3_GAIN, w,
+                               gy * lout.double()[:, :, None, None] if scaled else gy)
+    assert not scaled or OH * OW > CV.PRESCALE_MOD_PIX
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", "0")
+    for flag, fused in (("1", 1), ("0", 0)):
+        monkeypatch.setenv("IDEAS_BF16_WGRAD3", flag)
+        assert _lib.load().ideas_bf16_wgrad3_supported(C.byref(p)) == fused, (case, flag)
+        out = torch.full((co, ci, 3, 3), 0.5, device="cuda").contiguous(memory_format=CL)
+        got = CV.conv_wgrad_raw(dev(gy, dtype=BF), dev(x, dtype=BF), g, (co, ci, 3, 3), WGRAD3_GAIN,
+                                None if lin is None else lin.cuda(), None if lout is None else lout.cuda(), out=out)
+        assert got.dtype == torch.float32
+        err = rel_err(got - 0.5, ref)
+        print("wgrad3 case", case, "tap-fused" if fused else "generic", "rel err %.3e" % err)
+        assert err < 2e-5, (case, "tap-fused" if fused else "generic", err)
+
+
+def test_bf16_8wave_tile_full_epilogue_vs_f64(fwd_launches):
+    """The 8-wave 256 x 128 tile of conv_bf16_kernel with bias, leaky-ReLU and the residual merge together (the "ba_resid" form of
+    test_pointwise_flat_kernel_bf16_is_bitwise_the_generic_kernel) on 32 -> 256 channels, 3x3 / stride 2 from 33 x 33 (512 rows),
+    against f64 on the bf16-rounded operands."""
+    import ideas_amd.op.conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom
+    B, ci, co, H = 2, 32, 256, 33
+    torch.manual_seed(B + ci + co + H)
+    x = bf(torch.randn(B, ci, H, H, dtype=torch.float64))
+    w = bf(torch.randn(co, ci, 3, 3, dtype=torch.float64))
+    bias = torch.randn(co, dtype=torch.float64).float().double() * 0.3
+    y = F.leaky_relu(F.conv2d(x, w * 0.06, stride=2) + bias.view(1, -1, 1, 1), 0.2) * 1.3
+    resid = bf(torch.randn_like(y))
+    y = (y + resid) * 0.7
+    yd = CV.conv_fwd_raw(dev(x, dtype=BF), dev(w.float()), ConvGeom(3, 3, 2, 0, False), 0.06, bias=dev(bias.float()), act=True, act_gain=1.3,
+                         alpha=0.2, resid=dev(resid, dtype=BF), resid_gain=0.7)
+    assert_8wave(fwd_launches, "single")
+    assert yd.dtype == BF and tuple(yd.shape) == tuple(y.shape)
+    close_bf16(yd, y, "y", roundings=2)
+
+
 def test_bf16_tap_fused_weight_gradient_partial_last_part(monkeypatch):
     """conv_bf16_wgrad3_kernel where an image's rows do NOT divide into its parts: 512 -> 512 at 104 x 128, B = 2 is the smallest
     shape the dispatch gives to the tap-fused kernel (>= 6e9 products) with several parts -- three of 35 rows, the last one 34.
     Against f64 on the same bf16 operands within the bound of test_tiny_spatial_weight_gradient_vs_f64 (f32 accumulation of exact
     bf16 products), and against the generic kernel as in the full-size test below."""
+    import ctypes
     import ideas_amd.op.conv as CV
-    from ideas_amd.op.conv_plan import ConvGeom
+    from ideas_amd import _lib
+    from ideas_amd.op.conv_plan import ConvGeom, plan_wgrad
     torch.manual_seed(11)
     B, C, H, W = 2, 512, 104, 128
     g = ConvGeom(3, 3, 1, 1, False)
     x = torch.randn(B, C, H, W, device="cuda").to(BF).contiguous(memory_format=CL)
     gy = torch.randn(B, C, H, W, device="cuda").to(BF).contiguous(memory_format=CL)
     gain = 1 / math.sqrt(C * 9)
+    pw = CV._params(plan_wgrad(x.shape, gy.shape, g), gain)
+    monkeypatch.delenv("IDEAS_BF16_WGRAD3_MIN_WORK", raising=False)         # the default floor
     out = {}
     for flag in ("1", "0"):
         monkeypatch.setenv("IDEAS_BF16_WGRAD3", flag)
+        assert _lib.load().ideas_bf16_wgrad3_supported(ctypes.byref(pw)) == int(flag)
         out[flag] = CV.conv_wgrad_raw(gy, x, g, (C, C, 3, 3), gain)
     xp = F.pad(x.double(), [1] * 4)
     gyd = gy.double().reshape(B, C, H * W)
@@ -233,12 +434,18 @@ def test_bf16_image_and_tap_fused_kernels_full_size(monkeypatch):
     """BASELINE-size check of the round-3 bf16 kernels on G.layers.7.conv2's shape (modulated 128 -> 128 at 256x256, B = 4): the LDS
     image kernel (forward, input gradient) and the tap-fused weight gradient against the generic kernels they replace on the same
     operands (same bf16 products, f32 accumulation in another order: a few results land on the other side of a bf16 rounding), and
-    the adjoint identity <gy, conv(x)> == <dgrad(gy), x> between the two image-kernel launches."""
+    the adjoint identity <gy, conv(x)> == <dgrad(gy), x> between the two image-kernel launches.  At B = 4 the layer has 2^32
+    products, under the 6e9 floor of the tap-fused kernel's dispatch (the step runs it at B = 32): the floor is moved to 0 here and
+    ideas_bf16_wgrad3_supported confirms which weight-gradient kernel each pass runs."""
+    import ctypes
     import ideas_amd.op.conv as CV
-    from ideas_amd.op.conv_plan import ConvGeom
+    from ideas_amd import _lib
+    from ideas_amd.op.conv_plan import ConvGeom, plan_wgrad
     torch.manual_seed(3)
     B, C, R = 4, 128, 256
     g = ConvGeom(3, 3, 1, 1, False)
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", "0")
+    pw = CV._params(plan_wgrad((B, C, R, R), (B, C, R, R), g), 1.0)
     x = torch.randn(B, C, R, R, device="cuda").to(BF).contiguous(memory_format=CL)
     gy = torch.randn(B, C, R, R, device="cuda").to(BF).contiguous(memory_format=CL)
     w = torch.randn(C, C, 3, 3, device="cuda").contiguous(memory_format=CL)
@@ -249,6 +456,7 @@ def test_bf16_image_and_tap_fused_kernels_full_size(monkeypatch):
     for flag in ("1", "0"):
         monkeypatch.setenv("IDEAS_BF16_IMG", flag)
         monkeypatch.setenv("IDEAS_BF16_WGRAD3", flag)
+        assert _lib.load().ideas_bf16_wgrad3_supported(ctypes.byref(pw)) == int(flag)
         out[flag] = (CV.conv_fwd_raw(x, w, g, gain, s, d), CV.conv_dgrad_raw(gy, w, g, (R, R), gain, d, s),
                      CV.conv_wgrad_raw(gy, x, g, tuple(w.shape), gain, s, d))
     for a, b, what in zip(out["1"], out["0"], ("y", "gx", "gw")):
@@ -261,8 +469,11 @@ def test_bf16_image_and_tap_fused_kernels_full_size(monkeypatch):
     assert abs(lhs - rhs) <= 2e-3 * max(abs(lhs), abs(rhs), float((gy.double() * y).abs().sum()) * 1e-3)
 
 
-@pytest.mark.parametrize("case", [(2, 64, 32, 1, 2, 16, 16), (2, 32, 64, 3, 2, 9, 9), (2, 128, 128, 3, 2, 16, 16)])
-def test_conv_transpose_bf16(ops, bf16_mode, case):
+CONVT_8WAVE = (2, 32, 256, 3, 2, 16, 16)     # four parity phases of 256 channels, 2 x 17 x 17 rows at most: the 8-wave tile in the multi kernel
+
+
+@pytest.mark.parametrize("case", [(2, 64, 32, 1, 2, 16, 16), (2, 32, 64, 3, 2, 9, 9), (2, 128, 128, 3, 2, 16, 16), CONVT_8WAVE])
+def test_conv_transpose_bf16(ops, bf16_mode, fwd_launches, case):
     B, ci, co, k, s, H, W = case
     torch.manual_seed(sum(case))
     x = bf(torch.randn(B, ci, H, W, dtype=torch.float64)).requires_grad_(True)
@@ -273,6 +484,8 @@ def test_conv_transpose_bf16(ops, bf16_mode, case):
     gx, gw = torch.autograd.grad(y, (x, w), gy)
     xd, wd = dev(x, dtype=BF).requires_grad_(True), dev(w.float()).requires_grad_(True)
     yd = ops.conv_transpose2d(xd, wd, None, stride=s, gain=scale)
+    if case == CONVT_8WAVE:
+        assert_8wave(fwd_launches, "multi")
     close_bf16(yd, y, ("y", case))
     gxd, gwd = torch.autograd.grad(yd, (xd, wd), dev(gy, dtype=BF))
     close_bf16(gxd, gx, ("gx", case))
@@ -280,8 +493,11 @@ def test_conv_transpose_bf16(ops, bf16_mode, case):
 
 
 @pytest.mark.parametrize("case", [(2, 64, 128, False, 16), (2, 128, 64, True, 16), (3, 32, 96, False, 12), (2, 96, 96, True, 9),
-                                  (2, 128, 128, False, 32), (3, 128, 160, False, 64)])     # (32, 64 wide: conv_bf16_img_kernel, per-sample packs)
-def test_modconv_bf16_vs_f64(ops, bf16_mode, case):
+                                  (2, 128, 128, False, 32), (3, 128, 160, False, 64),      # (32, 64 wide: conv_bf16_img_kernel, per-sample packs)
+                                  # the 8-wave tile with per-sample packs: 289 rows an image (two tiles an image, the second
+                                  # clamped at the image's end), and inside the multi kernel (phases of 17 x 17 rows at most)
+                                  (2, 32, 256, False, 17), (2, 32, 256, True, 16)])
+def test_modconv_bf16_vs_f64(ops, bf16_mode, fwd_launches, case):
     """Modulated conv (same-resolution, and transposed + blur): the block-level weight modulation of csrc/conv_bf16.hip, the
     per-image tiling for sizes that are not a multiple of the tile, and the per-image split of the weight gradient.
     Reference: f64 in the reference's own association (per-sample weights w * s, stylegan2/model.py:240-248); tolerance
@@ -308,6 +524,10 @@ def test_modconv_bf16_vs_f64(ops, bf16_mode, case):
     xd, wd = dev(x, dtype=BF).requires_grad_(True), dev(w.float(), cl=False).requires_grad_(True)
     sd = dev(st.float()).requires_grad_(True)
     yd = ops.modulated_conv2d(xd, wd, sd, demodulate=True, upsample=up, fir=dev(fir.float()))
+    if co == 256:
+        assert_8wave(fwd_launches, "multi" if up else "single", per_image=1)
+    if not up and H in (32, 64):        # the library's word for the LDS-image kernel: its patch width for the forward launch
+        assert [e[2:] for e in fwd_launches] == [(1, (128, 128, 4), H)], fwd_launches
     assert yd.dtype == BF
     assert rel_err(yd, y) < 1.5e-2, ("y", case, rel_err(yd, y))
     gxd, gwd, gsd = torch.autograd.grad(yd, (xd, wd, sd), dev(gy, dtype=BF))

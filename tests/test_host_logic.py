@@ -116,6 +116,115 @@ def test_splitk_plans_match_pinned():
         assert hashlib.sha256(rows.tobytes()).digest() == bytes(g[name + "/sha256"]), name
 
 
+def _wgrad3_params(B, ci, co, OH, OW, pad=1, stride=1):
+    """ideas_conv_params of the weight-gradient launch of a 3x3 conv whose output is OH x OW (op/conv_plan.py::plan_wgrad)."""
+    import ideas_amd.op.conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom, plan_wgrad
+    ih, iw = (OH - 1) * stride + 3 - 2 * pad, (OW - 1) * stride + 3 - 2 * pad
+    return CV._params(plan_wgrad((B, ci, ih, iw), (B, co, OH, OW), ConvGeom(3, 3, stride, pad, False)), 1.0)
+
+
+def test_bf16_wgrad3_query_and_work_floor(monkeypatch):
+    """ideas_bf16_wgrad3_supported (csrc/conv_bf16.hip: the function ideas_bf16_wgrad itself asks before it launches
+    conv_bf16_wgrad3_kernel) and the floor IDEAS_BF16_WGRAD3_MIN_WORK under it.  Unset, the dispatch is what it always was: 6e9
+    products, so the small 3x3 / stride-1 shapes of test_bf16_gpu.py::CONV_CASES are the generic kernel's and 512 -> 512 at
+    104 x 128, B = 2 the tap-fused one's.  At 0 every row of WGRAD3_CASES is admitted (what test_bf16_tap_fused_weight_gradient_vs_f64 rests
+    on), IDEAS_BF16_WGRAD3=0 refuses everything, each geometric condition refuses alone, and the plan query gives every row the
+    parts, rows per part and strips it names."""
+    from ideas_amd import _lib
+    from test_bf16_gpu import WGRAD3_CASES, WGRAD3_OP_CASES, wgrad3_launch
+    lib = _lib.load()
+    q = lambda p: lib.ideas_bf16_wgrad3_supported(ctypes.byref(p))
+    # (B, Cin, Cout, OH, OW).  The third small one is the shape of test_bf16_image_and_tap_fused_kernels_full_size, G.layers.7.conv2 at
+    # B = 4: 2^32 = 4.3e9 products, under the floor -- that test moves the floor to reach the kernel; the layer at the bench's B = 32
+    # and the 104 x 128 test's shape are over it
+    small = [(3, 64, 64, 40, 96), (2, 128, 128, 16, 32), (4, 128, 128, 256, 256)]
+    big = [(2, 512, 512, 104, 128), (32, 128, 128, 256, 256)]
+    for var in ("IDEAS_BF16_WGRAD3_MIN_WORK", "IDEAS_BF16_WGRAD3"):
+        monkeypatch.delenv(var, raising=False)
+    assert [q(_wgrad3_params(*s)) for s in small] == [0, 0, 0] and [q(_wgrad3_params(*s)) for s in big] == [1, 1]
+    assert [s[0] * s[3] * s[4] * s[1] * s[2] >= 6000000000 for s in small + big] == [False, False, False, True, True]
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", "6000000000")      # the default, spelled out
+    assert [q(_wgrad3_params(*s)) for s in small + big] == [0, 0, 0, 1, 1]
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", str(2 * 512 * 512 * 104 * 128 + 1))      # the floor is the number given
+    assert [q(_wgrad3_params(*s)) for s in big] == [0, 1]
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", str(2 * 512 * 512 * 104 * 128))
+    assert [q(_wgrad3_params(*s)) for s in big] == [1, 1]
+    assert lib.ideas_bf16_wgrad3_supported(None) == 0
+
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3_MIN_WORK", "0")
+    rows = [wgrad3_launch(case)[3] for case, _ in WGRAD3_CASES]
+    rows += [_wgrad3_params(B, ci, co, H, W) for B, ci, co, k, s, pad, refl, H, W in WGRAD3_OP_CASES] + [_wgrad3_params(*s) for s in small + big]
+    assert all(q(p) == 1 for p in rows)
+    assert {(p.offy, p.offx) for p in rows} == {(-1, -1), (0, 0), (-2, -2)} and {p.reflect for p in rows} == {0, 1}
+    # each geometric condition, broken alone on an admitted shape
+    ok = (2, 64, 64, 8, 32)
+    assert q(_wgrad3_params(*ok)) == 1
+    for what, p in (("OW % 32", _wgrad3_params(2, 64, 64, 8, 48)), ("OW % 32", _wgrad3_params(2, 64, 64, 8, 16)),
+                    ("Cin % 64", _wgrad3_params(2, 32, 64, 8, 32)), ("Cin % 64", _wgrad3_params(2, 96, 64, 8, 32)),
+                    ("Cout % 64", _wgrad3_params(2, 64, 32, 8, 32)), ("Cout % 64", _wgrad3_params(2, 64, 96, 8, 32)),
+                    ("OH < 8", _wgrad3_params(2, 64, 64, 7, 32)), ("stride 2", _wgrad3_params(2, 64, 64, 8, 32, pad=0, stride=2)),
+                    ("offx = 1", None), ("offy = 1", None), ("offx = -3", _wgrad3_params(2, 64, 64, 8, 32, pad=3)), ("5 taps", None),
+                    ("dilation", None)):
+        if p is None:
+            p = _wgrad3_params(*ok)
+            if what.startswith("off"):
+                setattr(p, what[:4], 1)
+            elif what == "5 taps":
+                p.TX = 5
+            else:
+                p.dx = 2
+        assert q(p) == 0, what
+    monkeypatch.setenv("IDEAS_BF16_WGRAD3", "0")
+    assert not any(q(p) for p in rows)
+    monkeypatch.delenv("IDEAS_BF16_WGRAD3")
+    # the part structure the rows name: {strips x B x parts, rows per part, parts} from the launcher's own plan (site 6)
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for (B, ci, co, OH, OW, *_), (parts, per, strips) in WGRAD3_CASES:
+        assert OW == 32 * strips
+        got = splitk_plan_rows(raw, [(B, OH, OW, ci, co, 3, 0)], 6, 0)[0].tolist()
+        assert got == [strips * B * parts, per, parts, 512], ((B, ci, co, OH, OW), got)
+        assert (parts - 1) * per < OH <= parts * per               # every part has rows; the last one OH - (parts - 1) * per
+    last = {c[3]: c[3] - (pl[0] - 1) * pl[1] for c, pl in WGRAD3_CASES}
+    assert last[97] == 31 and last[65] == 32
+    assert sorted({(c[3] + 2) % 6 for c, _ in WGRAD3_CASES}) == [0, 1, 2, 3, 4, 5]      # every exit of the unrolled step loop
+
+
+def test_bf16_forward_tile_query():
+    """ideas_bf16_fwd_choice (the diagnostic beside the ABI, driven by bf16_fwd_tile itself): the 8-wave 256 x 128 tile exactly for
+    Cout >= 256 with >= 256 rows, rows counted per image for per-sample packs; the 4-wave ladder below it by Cout; and the LDS-image
+    kernel's claim on 3x3 / stride-1 launches reported beside the tile."""
+    import ideas_amd.op.conv as CV
+    from ideas_amd.op.conv_plan import ConvGeom, plan_fwd
+    from test_bf16_gpu import TILE_8WAVE, fwd_choice
+
+    def params(B, ci, co, H, W, k=3, stride=2, pad=0):
+        return CV._params(plan_fwd((B, ci, H, W), torch.empty(co, ci, k, k), ConvGeom(k, k, stride, pad, False)), 1.0)
+    p = params(1, 32, 256, 33, 33)                                  # 16 x 16 = 256 rows
+    assert (p.OH, p.OW) == (16, 16)
+    assert fwd_choice(p, 0) == (TILE_8WAVE, 0) and fwd_choice(p, 1) == (TILE_8WAVE, 0)
+    assert fwd_choice(params(1, 32, 252, 33, 33), 0)[0] == (128, 128, 4)           # 255 would break Cout % 4; the rule is Cout >= 256
+    p.Cout = 255
+    assert fwd_choice(p, 0)[0] == (128, 128, 4)
+    p = params(1, 32, 256, 33, 35)                                  # 16 x 17 = 272 rows
+    p.OH, p.OW = 15, 17                                             # 255 rows
+    assert fwd_choice(p, 0)[0] == (128, 128, 4)
+    p.OH, p.OW = 16, 16
+    assert fwd_choice(p, 0)[0] == TILE_8WAVE
+    p = params(2, 32, 256, 33, 31)                                  # 16 x 15 = 240 rows an image, 480 in all
+    assert fwd_choice(p, 0)[0] == TILE_8WAVE and fwd_choice(p, 1)[0] == (128, 128, 4)
+    p = params(3, 32, 512, 21, 21)                                  # 100 rows an image, 300 in all
+    assert fwd_choice(p, 0)[0] == TILE_8WAVE and fwd_choice(p, 1)[0] == (128, 128, 4)
+    for co, tile in ((1024, TILE_8WAVE), (256, TILE_8WAVE), (252, (128, 128, 4)), (68, (128, 128, 4)), (64, (128, 64, 4)),
+                     (36, (128, 64, 4)), (32, (128, 32, 4)), (4, (128, 32, 4))):
+        assert fwd_choice(params(2, 32, co, 33, 33), 0)[0] == tile, co
+    # the LDS-image kernel takes 3x3 / stride 1 / pad 1 at W % 16 == 0 and whole patches first: 16 x 16 in 16-wide patches, 8 x 64 in 64-wide
+    assert fwd_choice(params(1, 256, 384, 16, 16, 3, 1, 1), 0) == (TILE_8WAVE, 16)
+    assert fwd_choice(params(2, 64, 128, 8, 64, 3, 1, 1), 0) == ((128, 128, 4), 64)
+    assert fwd_choice(params(1, 32, 256, 17, 18, 3, 1, 1), 0) == (TILE_8WAVE, 0)       # 18 columns: the generic tile
+    assert fwd_choice(params(1, 256, 256, 16, 17, 1, 1, 0), 0) == (TILE_8WAVE, 0)
+
+
 def prep_plan_reference(op, a, s, w_addr):
     """What the commit before csrc/weight_prep.hip computed for a derived-weight job, transcribed from its three places: the entry
     points' validation (ideas_b3_split_weights_strided, ideas_b3_wino_split_weights, ideas_bf16_pack_weights_strided), op/conv.py's

@@ -4,35 +4,16 @@
 // JPEG file channel") and restated in numpy by tests/jpegfile_ref.py, which tests/test_jpeg_file.py holds to Pillow's own bytes.
 //
 // The lane mapping, tables, colour conversion, row I/O, tile walk and the block's way through LDS are jpeg_block.hpp's, shared with
-// attack.hip; this file holds the integer model's arithmetic (islow_arith), the kernels' plane logic (the 4:2:0 average, the triangle
-// upsampler) and the launchers.
+// attack.hip; the inverse pass and the triangle upsampler are jpeg_islow.hpp's, shared with the file reader (jpeg_decode.hip); this file
+// holds the forward pass, the quantiser (islow_arith), the 4:2:0 average and the launchers.
 //
 // 4:2:0 takes two launches, because the upsampler needs one chroma sample of halo across block borders: chroma420_kernel loads 16x16
 // pixels a block, converts, averages, round-trips Cb and Cr and writes the decoded half-resolution planes as bytes into the workspace;
 // jpeg_file_kernel round-trips the luma, reads the workspace with clamped neighbours, upsamples, converts and stores.  4:4:4 and C = 1
 // are jpeg_file_kernel alone.  DESIGN.md "Channel attacks".
-#include "jpeg_block.hpp"
+#include "jpeg_islow.hpp"
 
 namespace {
-
-// round(c * 2^13) of the twelve constants of the 8-point transform
-constexpr int F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633;
-constexpr int F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
-constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// The odd half both transforms share: (t4, t5, t6, t7) -> four rotated sums.  Every factor stays below 2^23 and every product below
-// 2^31 for what an encoder produces (tests/jpegfile_ref.py asserts it on every product), so the 24-bit multiply is exact.
-__device__ __forceinline__ void odd_part(int t4, int t5, int t6, int t7, int& a4, int& a5, int& a6, int& a7) {
-    const int z5 = __mul24(t4 + t6 + t5 + t7, F_1_175);
-    const int z1 = __mul24(t4 + t7, -F_0_899), z2 = __mul24(t5 + t6, -F_2_562);
-    const int z3 = __mul24(t4 + t6, -F_1_961) + z5, z4 = __mul24(t5 + t7, -F_0_390) + z5;
-    a4 = __mul24(t4, F_0_298) + z1 + z3;
-    a5 = __mul24(t5, F_2_053) + z2 + z4;
-    a6 = __mul24(t6, F_3_072) + z2 + z3;
-    a7 = __mul24(t7, F_1_501) + z1 + z4;
-}
 
 // FIRST: the row pass (results scaled up by 4); otherwise the column pass, which leaves 8 F
 template <bool FIRST> __device__ __forceinline__ void fdct_pass(const int (&d)[8], int (&o)[8]) {
@@ -53,21 +34,6 @@ template <bool FIRST> __device__ __forceinline__ void fdct_pass(const int (&d)[8
     int a4, a5, a6, a7;
     odd_part(t4, t5, t6, t7, a4, a5, a6, a7);
     o[7] = descale(a4, N); o[5] = descale(a5, N); o[3] = descale(a6, N); o[1] = descale(a7, N);
-}
-
-// FIRST: the column pass (DESCALE by 11); otherwise the row pass (by 18)
-template <bool FIRST> __device__ __forceinline__ void idct_pass(const int (&c)[8], int (&o)[8]) {
-    const int z1 = __mul24(c[2] + c[6], F_0_541);
-    const int t2 = z1 + __mul24(c[6], -F_1_847), t3 = z1 + __mul24(c[2], F_0_765);
-    const int t0 = (c[0] + c[4]) << CONST_BITS, t1 = (c[0] - c[4]) << CONST_BITS;
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    int a0, a1, a2, a3;
-    odd_part(c[7], c[5], c[3], c[1], a0, a1, a2, a3);
-    constexpr int N = FIRST ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS + 3;
-    o[0] = descale(t10 + a3, N); o[7] = descale(t10 - a3, N);
-    o[1] = descale(t11 + a2, N); o[6] = descale(t11 - a2, N);
-    o[2] = descale(t12 + a1, N); o[5] = descale(t12 - a1, N);
-    o[3] = descale(t13 + a0, N); o[4] = descale(t13 - a0, N);
 }
 
 // sign(c) ((|c| + den / 2) / den) with den = 8 T: the quotient by the f32 reciprocal (numerator below 2^24, so off by one at most),
@@ -237,31 +203,7 @@ __global__ __launch_bounds__(256) void jpeg_file_kernel(unsigned char* __restric
                             coef + (((plane * bhn + by) * bwn + bx) * 64 + r));
         }
         if constexpr (C == 3 && SUB == 2) {
-            // the triangle filter on the REAL ch x cw samples, neighbours clamped to them: s = 3 c(i, .) + c(i', .), i' the row above
-            // for an even output row and the one below for an odd one; columns 4 bx - 1 .. 4 bx + 4 serve this lane's 8 pixels
-            const int ch = (H + 1) >> 1, cw = (W + 1) >> 1;
-            const int yc = yy < H ? yy : H - 1;
-            const int i = yc >> 1;
-            const int i2 = (yc & 1) ? (i + 1 < ch ? i + 1 : ch - 1) : (i > 0 ? i - 1 : 0);
-            const bool plain = cw <= 2;                      // W <= 4: the library copies every chroma sample to its 2x2 pixels
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const unsigned char* c0 = half + ((b * 2 + p) * ch + i) * cw;
-                const unsigned char* c1 = half + ((b * 2 + p) * ch + i2) * cw;
-                int s[6], c[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    int j = 4 * bx - 1 + k;
-                    j = j < 0 ? 0 : (j > cw - 1 ? cw - 1 : j);
-                    c[k] = c0[j];
-                    s[k] = 3 * c[k] + (int)c1[j];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    pl[1 + p][2 * k] = plain ? c[k + 1] : (3 * s[k + 1] + s[k] + 8) >> 4;
-                    pl[1 + p][2 * k + 1] = plain ? c[k + 1] : (3 * s[k + 1] + s[k + 2] + 7) >> 4;
-                }
-            }
+            IDEAS_UPSAMPLE420_ROW(half, b, H, W, yy, bx, pl)
         }
 
         unsigned ob[8 * C];                                  // the bytes of this lane's row, pixel-major

@@ -1,8 +1,8 @@
 // The JPEG FILE, written on the device: from the quantised coefficients of ideas_jpeg_file_roundtrip (attack_jpeg.hip) to the bytes
 // libjpeg / libjpeg-turbo writes with its defaults -- header, Huffman coding with the Annex K tables, bit packing, byte stuffing.  The
 // stream is stated in include/ideas_hip.h ("The JPEG file, written") and restated in Python by tests/jpegbytes_ref.py, which
-// tests/test_jpeg_bytes.py holds to Pillow's own files.  jpeg_block.hpp gives the quantiser tables; nothing else of the round trip is
-// used here.
+// tests/test_jpeg_bytes.py holds to Pillow's own files.  jpeg_block.hpp gives the quantiser tables and jpeg_scan.hpp the walk over
+// the scan, shared with the reader (jpeg_decode.hip); nothing else of the round trip is used here.
 //
 // A block's code has a variable length, so the file is made in four launches behind one memset:
 //   code_kernel<false>   one thread a block of the scan, in scan order: the number of bits of its code.  The DC predictor and the dummy
@@ -19,13 +19,9 @@
 // DESIGN.md 3.15.1.
 #include <initializer_list>
 #include "jpeg_block.hpp"
+#include "jpeg_scan.hpp"
 
 namespace {
-
-// natural index 8 u + v of zigzag position k
-__device__ const unsigned char k_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ISO/IEC 10918-1 Annex K.3 - K.6: the number of codes of each length 1..16 and the symbols in order of their codes
 struct huff_spec {
@@ -138,30 +134,6 @@ __device__ __forceinline__ unsigned header_byte(int i, int C, int H, int W, int 
         v = C == 3 && sub == 2 ? 0x22u : 0x11u;
     }
     return v;
-}
-
-// The scan of one image: MCUs in raster order, in each the hs x hs luma blocks in raster order, then Cb, then Cr.
-struct scan_geom {
-    int C, hs, per_mcu;            // per_mcu = hs * hs + (C == 3 ? 2 : 0) blocks
-    int mw;                        // MCU columns
-    int bhn, bwn;                  // the luma block grid of coef_y
-    int64_t nmcu, nblk;            // MCUs (= the chroma block grid of coef_c) and blocks of one image
-};
-
-// The luma block (by, bx) of coef_y whose DC scan block `slot` of MCU (my, mx) carries: the block itself where it exists.  A block right
-// of the grid is a dummy with the DC of the block on its left; a block below it one with the DC of slot (0, 1), itself a dummy where
-// the grid is short on the right too.  Slot 0 always exists.
-__device__ __forceinline__ bool luma_source(const scan_geom& g, int my, int mx, int slot, int& by, int& bx) {
-    by = my * g.hs + (g.hs == 2 ? slot >> 1 : 0);
-    bx = mx * g.hs + (g.hs == 2 ? slot & 1 : 0);
-    const bool real = by < g.bhn && bx < g.bwn;
-    if (by >= g.bhn) {
-        by = my * 2;
-        bx = min(mx * 2 + 1, g.bwn - 1);
-    } else if (bx >= g.bwn) {
-        bx -= 1;
-    }
-    return real;
 }
 
 // the number of bits of |v|: the category of a DC difference or an AC coefficient
@@ -299,29 +271,6 @@ __global__ __launch_bounds__(256) void code_kernel(uint64_t* __restrict__ offs, 
     }
 }
 
-// Exclusive prefix sum of one value a thread over the workgroup of 256; total = the sum.  s_w: 4 words of LDS.  Two barriers; the
-// first one also ends the previous call's reads of s_w.
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* s_w, unsigned& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        before += i < wave ? s_w[i] : 0u;
-        total += s_w[i];
-    }
-    return before + inc - v;
-}
-
 // offs[image][0 .. nblk): counts in, exclusive prefix sums out; bits[image] = their sum.  One workgroup an image, 4 blocks a thread a
 // trip (at most 1024 * 1660 bits: 32 bits hold a trip's sum), the carry in 64 bits.
 __global__ __launch_bounds__(256) void scan_kernel(uint64_t* __restrict__ offs, uint64_t* __restrict__ bits, int64_t nblk) {
@@ -416,15 +365,8 @@ struct enc_plan {
 enc_plan plan_for(int B, int C, int H, int W, int sub) {
     enc_plan p;
     if ((C != 1 && C != 3) || H <= 0 || W <= 0 || H > 65535 || W > 65535 || (sub != 0 && sub != 2)) return p;
-    scan_geom& g = p.g;
-    g.C = C;
-    g.hs = C == 3 && sub == 2 ? 2 : 1;
-    g.per_mcu = g.hs * g.hs + (C == 3 ? 2 : 0);
-    g.mw = (int)ideas_cdiv(W, 8 * g.hs);
-    g.bhn = (int)ideas_cdiv(H, 8);
-    g.bwn = (int)ideas_cdiv(W, 8);
-    g.nmcu = ideas_cdiv(H, 8 * g.hs) * g.mw;
-    g.nblk = g.nmcu * g.per_mcu;
+    p.g = make_scan_geom(C, H, W, sub);
+    const scan_geom& g = p.g;
     p.hdr = C == 3 ? HDR_3 : HDR_1;
     p.max_bytes = p.hdr + 416 * g.nblk + 3;
     const int64_t nb = B > 0 ? B : 1;

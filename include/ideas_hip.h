@@ -800,6 +800,52 @@ int ideas_jpeg_file_encode(void* files, int* nbytes, long long row_stride, const
                            int B, int C, int H, int W, int quality, int subsampling, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The JPEG file, read, csrc/jpeg_decode.hip: from the entropy-coded segment of B baseline files to their quantised coefficients and
+ * to the pixels libjpeg / libjpeg-turbo decodes -- Pillow's Image.open, to the byte.  tests/jpegdecode_ref.py restates it in Python
+ * and tests/test_jpeg_decode.py holds that restatement to Pillow's own pixels.  The header of a file is read on the host
+ * (ideas_amd/op/jpeg_decode.py::parse_jpeg), which hands over:
+ *   scans: uint8 [B][row_stride].  Row b holds the entropy-coded segment of file b, starting at the first byte after the SOS header and
+ *     still stuffed; nbytes[b] bytes of it are valid.  The scan ends at the first FF xx with xx != 00 (normally FFD9), or at nbytes[b]
+ *     if there is none (an FF that is the last valid byte is a byte of data).
+ *   qt: uint16 [B][C][64], one dequantisation table per image AND per component, in natural order (index 8 u + v, as coef_*), values
+ *     1..255: the host resolves the table selectors, and images of different quality can share a call.
+ *   huff: [C][2][16 + 256] bytes, for each component its DC and its AC table as the 16 counts and the symbols of a DHT segment, resolved
+ *     on the host.  One set per call.
+ *   out_u8, y, coef_y (optional), coef_c (optional): as in ideas_jpeg_file_roundtrip, in its layouts.
+ *   status[b]: 0 = decoded, -1 = corrupt.
+ * C, subsampling, H, W and the MCU, dummy-block and DC-predictor rules are those of "The JPEG file, written" above: a dummy luma block
+ * is decoded and dropped, its DC difference counts for the predictor.
+ * Corrupt means any of: a bit pattern that is no code of its table; an AC category above 10 or a DC category above 11; a run that
+ * passes coefficient 63 (a ZRL counts as a run with a coefficient behind it); a DC outside +-2047 after prediction; the data ending
+ * before the last block, i.e. a symbol of a block of the scan that would START at or behind the end of the data; nbytes[b] outside
+ * 0..row_stride (the lengths live on the device, so the host cannot refuse them).  An AC symbol 0x10..0xE0 ends the block, as in the
+ * library.  A corrupt image's outputs are unspecified but stay inside its rows; the other images of the batch are not affected.
+ * Bits after the last block are ignored.  Bits read past the end of the data count as 1.
+ * Pixels: steps 7-9 of the file channel with the file's tables, promised to the byte for every file whose coefficients keep the
+ * transform inside the bounds tests/jpegfile_ref.py asserts -- every file an encoder made from 8-bit pixels.  Outside them the pixels
+ * are unspecified, but the coefficients are still exact and no access leaves a buffer (signed arithmetic wraps: -fwrapv).
+ * How: the clean stream is cut into subsequences of IDEAS_JPEG_SUBSEQ_BITS bits.  The decoder's state between two symbols is (bit
+ * position, slot of the block in its MCU, zigzag index); one workgroup an image iterates in_i = out_{i-1}, out_i = f_i(in_i) from the
+ * guesses in_i = (i L, 0, 0) until nothing changes -- after round r subsequences 0..r are exact, so nsub + 1 rounds are the hard limit
+ * and the fixed point does not depend on scheduling; Huffman streams re-synchronise by themselves, so files need few rounds.  Launches
+ * behind two to three memsets: unstuff, synchronise, emit (one thread a subsequence: AC values and DC differences), DC prefix sum,
+ * pixels (two launches at 4:2:0 with C = 3).  Every grid is exact.  A symbol consumes 1..27 bits, so every inner loop is bounded by
+ * the subsequence length + 27 bits whatever the bytes are.
+ * workspace: ideas_jpeg_file_decode_workspace_bytes (0 for refused arguments), any alignment, any contents.  An image keeps at most
+ * min(row_stride, 208 blocks + 8) clean bytes (what its blocks can need); that many bits must fit 31 bits.  Nothing is written outside
+ * out_u8, y, coef_*, status and workspace.
+ * IDEAS_E_NULL: out_u8, status, scans, nbytes, qt, huff or workspace is NULL.  IDEAS_E_SHAPE: B, H or W <= 0, H or W > 65535, C other
+ * than 1 or 3, row_stride < 1, a size the size query answers with 0.  IDEAS_E_UNSUPPORTED: subsampling other than 0 or 2.  Every
+ * check comes before any launch.  (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#ifndef IDEAS_JPEG_SUBSEQ_BITS          /* (-DIDEAS_JPEG_SUBSEQ_BITS=n: a build for tools/bench_jpeg_decode.py to compare) */
+#define IDEAS_JPEG_SUBSEQ_BITS 1024
+#endif
+size_t ideas_jpeg_file_decode_workspace_bytes(int B, int C, int H, int W, int subsampling, long long row_stride);
+int ideas_jpeg_file_decode(void* out_u8, float* y, short* coef_y, short* coef_c, int* status, const void* scans, const int* nbytes,
+                           long long row_stride, const unsigned short* qt, const unsigned char* huff, void* workspace, int B, int C,
+                           int H, int W, int subsampling, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Spatial channel attacks on the 8-bit container, csrc/attack_spatial.hip: rescaling, Gaussian filtering and median filtering, what
  * a messenger or an image host does to a picture before it re-encodes it.  Integer arithmetic throughout: every result is defined
  * to the byte (tests/spatial_ref.py restates it in numpy; the resize is Pillow's Image.resize(size, Image.BILINEAR) on 8-bit

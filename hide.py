@@ -2,7 +2,8 @@
 """Hide a file in synthesised images (the sender of IDEAS: payload bits -> secret tensor -> Gstru -> G -> 8-bit PNGs).
 
     python hide.py --ckpt CHECKPOINT --payload FILE --out DIR [--sigma 1] [--delta 0.5] [--seed 0] [--batch 32] [--ecc RATE]
-                   [--format png|jpeg] [--jpeg_quality 90] [--jpeg_subsampling 420|444] [--jpeg_encoder pillow|device]
+                   [--format png|jpeg] [--png_encoder pillow|device] [--jpeg_quality 90] [--jpeg_subsampling 420|444]
+                   [--jpeg_encoder pillow|device]
 
 The payload is framed (4-byte length, CRC32, payload, random padding: ``ideas_amd.stego.frame``) into whole images of
 ``N * (image_size / 16)^2 * sigma`` bits each and written as ``DIR/000000.png``, ``DIR/000001.png``, ...  ``extract.py`` with the same
@@ -18,6 +19,11 @@ to expect behind it; use ``--ecc``.  ``--jpeg_encoder device`` writes the files 
 the GPU, one copy a batch brings the finished files over, and Pillow is not in the loop.  They are the files Pillow writes, byte for
 byte (a one-channel container at ``420`` differs in one header byte, the sampling factors, which Pillow sets to 2x2 and the device
 leaves at 1x1; both decode alike).
+
+``--png_encoder device`` (with the default ``--format png``) writes the files of ``op.png_file_encode`` instead of Pillow's: row filters,
+Huffman coding and checksums run on the GPU and one copy a batch brings the finished files over.  They hold the same pixels, so
+``extract.py`` reads the same payload, but not the same bytes: the device's deflate stream has no matches (include/ideas_hip.h, "The PNG
+file, written"), which costs photograph-like images next to nothing and a flat image one bit a byte.
 """
 import argparse
 import os
@@ -40,6 +46,9 @@ def main(argv=None):
     parser.add_argument("--jpeg_subsampling", choices=("420", "444"), default="420", help="with --format jpeg: the chroma subsampling")
     parser.add_argument("--jpeg_encoder", choices=("pillow", "device"), default="pillow",
                         help="with --format jpeg: who writes the files, Pillow on the host or the entropy coder on the GPU (the same bytes)")
+    parser.add_argument("--png_encoder", choices=("pillow", "device"), default="pillow",
+                        help="with --format png: who writes the files, Pillow on the host or the filters and the Huffman coder on the "
+                             "GPU (the same pixels, other bytes)")
     opt = parser.parse_args(argv)
     if not 1 <= opt.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality: {opt.jpeg_quality} is outside 1..100")
@@ -50,7 +59,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("hide.py needs a GPU (ideas_amd has no CPU path)")
     from ideas_amd import stego
-    from ideas_amd.op import jpeg_file_encode, jpeg_files_to_host, quantize_image
+    from ideas_amd.op import jpeg_file_encode, jpeg_files_to_host, png_file_encode, png_files_to_host, quantize_image
 
     device = torch.device("cuda")
     models, args = stego.load_models(opt.ckpt, device)
@@ -72,7 +81,8 @@ def main(argv=None):
     gen = torch.Generator(device=device).manual_seed(opt.seed)
     os.makedirs(opt.out, exist_ok=True)
     print(f"capacity per image: {room}; payload {len(payload)} bytes -> {rows.shape[0]} image(s)")
-    on_device, written = opt.format == "jpeg" and opt.jpeg_encoder == "device", 0
+    on_device, written = (opt.jpeg_encoder if opt.format == "jpeg" else opt.png_encoder) == "device", 0
+    ext = "jpg" if opt.format == "jpeg" else "png"
     if not on_device:
         from PIL import Image
     for i0 in range(0, rows.shape[0], opt.batch):
@@ -80,9 +90,12 @@ def main(argv=None):
         images, _ = stego.hide(models, args, bits, opt.sigma, opt.delta, generator=gen)
         u8, _ = quantize_image(images, dequantize=False)
         if on_device:
-            files = jpeg_files_to_host(*jpeg_file_encode(u8, opt.jpeg_quality, 2 if opt.jpeg_subsampling == "420" else 0))
+            if opt.format == "jpeg":
+                files = jpeg_files_to_host(*jpeg_file_encode(u8, opt.jpeg_quality, 2 if opt.jpeg_subsampling == "420" else 0))
+            else:
+                files = png_files_to_host(*png_file_encode(u8))
             for k, data in enumerate(files):
-                with open(os.path.join(opt.out, f"{i0 + k:06d}.jpg"), "wb") as f:
+                with open(os.path.join(opt.out, f"{i0 + k:06d}.{ext}"), "wb") as f:
                     f.write(data)
                 written += len(data)
             continue

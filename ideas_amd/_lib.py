@@ -81,6 +81,7 @@ LPIPS_MAX_PARTIALS = 64     # include/ideas_hip.h::IDEAS_LPIPS_MAX_PARTIALS
 POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1_VALID = 0, 1, 2     # include/ideas_hip.h::IDEAS_POOL_*
 FEATURE_STATS_MAX_DIM = 4096     # include/ideas_hip.h::IDEAS_FEATURE_STATS_MAX_DIM
 JPEG_SUBSEQ_BITS = 1024     # include/ideas_hip.h::IDEAS_JPEG_SUBSEQ_BITS
+PNG_STRIPE_ROWS = 32     # include/ideas_hip.h::IDEAS_PNG_STRIPE_ROWS
 PATH_LERP, PATH_SLERP, PATH_MAX_DIM = 0, 1, 4096     # include/ideas_hip.h::IDEAS_PATH_*
 
 _P = C.c_void_p
@@ -173,6 +174,9 @@ _PROTOS = {
     "ideas_jpeg_file_encode": (C.c_int, [_P, _P, C.c_longlong, _P, _P, _P] + [C.c_int] * 6 + [_P]),
     "ideas_jpeg_file_decode_workspace_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_longlong]),
     "ideas_jpeg_file_decode": (C.c_int, [_P] * 7 + [C.c_longlong, _P, _P, _P] + [C.c_int] * 5 + [_P]),
+    "ideas_png_file_max_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ideas_png_file_encode_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ideas_png_file_encode": (C.c_int, [_P, _P, C.c_longlong, _P, _P] + [C.c_int] * 4 + [_P]),
     "ideas_resample_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "ideas_median_u8": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
     "ideas_ecc_encode": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),

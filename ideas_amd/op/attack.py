@@ -118,17 +118,27 @@ def jpeg_file_encode(u8: torch.Tensor, quality: int, subsampling="4:2:0", return
     return (files, nbytes, out, y) if return_decoded else (files, nbytes)
 
 
+def _rows_to_host(files: torch.Tensor, nbytes: torch.Tensor, what: str):
+    """``(files, nbytes)`` of a file writer on the host -> (uint8 array ``[B, 4 + max_bytes]``, the lengths riding in front of the
+    rows; the lengths int32 ``[B]``), or None for B = 0.  ONE device-to-host copy and no synchronisation in front of it: the rows go
+    over whole (the longest file is not known on the host)."""
+    _lib.require_cuda(files, nbytes)
+    if files.dtype != torch.uint8 or files.dim() != 2 or nbytes.dtype != torch.int32 or tuple(nbytes.shape) != (files.shape[0],):
+        raise RuntimeError(f"{what} expects uint8 [B, max_bytes] and int32 [B], got {files.dtype} {tuple(files.shape)} and "
+                           f"{nbytes.dtype} {tuple(nbytes.shape)}")
+    if files.shape[0] == 0:
+        return None
+    host = torch.cat((nbytes.view(torch.uint8).view(-1, 4), files), dim=1).cpu().numpy()
+    return host, host[:, :4].copy().view("<i4")[:, 0]
+
+
 def jpeg_files_to_host(files: torch.Tensor, nbytes: torch.Tensor) -> List[bytes]:
     """``jpeg_file_encode``'s ``(files, nbytes)`` as a list of ``bytes``, one file each.  ONE device-to-host copy and no
     synchronisation in front of it: the lengths ride in front of the rows, whole (the longest file is not known on the host)."""
-    _lib.require_cuda(files, nbytes)
-    if files.dtype != torch.uint8 or files.dim() != 2 or nbytes.dtype != torch.int32 or tuple(nbytes.shape) != (files.shape[0],):
-        raise RuntimeError(f"jpeg_files_to_host expects uint8 [B, max_bytes] and int32 [B], got {files.dtype} {tuple(files.shape)} and "
-                           f"{nbytes.dtype} {tuple(nbytes.shape)}")
-    if files.shape[0] == 0:
+    rows = _rows_to_host(files, nbytes, "jpeg_files_to_host")
+    if rows is None:
         return []
-    host = torch.cat((nbytes.view(torch.uint8).view(-1, 4), files), dim=1).cpu().numpy()
-    lengths = host[:, :4].copy().view("<i4")[:, 0]
+    host, lengths = rows
     if (lengths < 0).any():
         raise RuntimeError(f"jpeg_files_to_host: image(s) {[int(i) for i in (lengths < 0).nonzero()[0]]} hold a coefficient that has no "
                            "Huffman code")

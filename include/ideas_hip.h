@@ -800,6 +800,63 @@ int ideas_jpeg_file_encode(void* files, int* nbytes, long long row_stride, const
                            int B, int C, int H, int W, int quality, int subsampling, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The PNG file, written, csrc/png_bytes.hip: the 8-bit container u8 [B][H][W][C] (C = 1 or 3) as B PNG files that any reader opens to
+ * exactly those pixels.  Lossless, and defined to the byte: tests/png_ref.py restates it in numpy and tests/test_png_file.py holds
+ * that restatement to zlib's inflate and Pillow's reader.  The deflate stream codes every filtered byte as a Huffman literal: there
+ * are NO matches (LZ77), so these are not the bytes zlib would write, and a flat image costs one bit a byte.  The file:
+ *   1. The signature 89 'PNG' 0D 0A 1A 0A.
+ *   2. IHDR (length 13): W and H as four bytes each (big-endian, as every integer of the framing), bit depth 8, colour type 0 (C = 1)
+ *      or 2 (C = 3), compression 0, filter 0, interlace 0.
+ *   3. ONE IDAT, then IEND; no other chunk.  Every chunk is length, type, data, CRC-32 of type and data.
+ *   4. IDAT's data is a zlib stream: 78 01, the deflate blocks, the Adler-32 of the filtered bytes.
+ *   Filtered bytes: per row one type byte 0..4 (None, Sub, Up, Average, Paeth), then the W C residuals (x - prediction) mod 256 with
+ *     a the byte C places to the left (bpp = C), b the byte above, c the byte above a; what lies left of the row or above the image is 0.
+ *     Average predicts floor((a + b) / 2); Paeth as in the PNG specification: p = a + b - c, the nearest of a, b, c to p, ties in that
+ *     order.  b and c are RAW bytes of the row above, so rows do not depend on each other's choice.  The type of a row is the one with
+ *     the least sum of |residual|, a residual read as int8 (r < 128 ? r : 256 - r); a tie goes to the lowest type.
+ *   Blocks: one deflate block per stripe of IDEAS_PNG_STRIPE_ROWS consecutive rows (the last stripe may be shorter), every block
+ *     BTYPE = 2 (dynamic Huffman), BFINAL on the last; the blocks follow each other bit by bit, and the last byte is padded with zeros.
+ *     A block is its header, the literal of every filtered byte of the stripe in order, and symbol 256.
+ *   The stripe's literal code: over symbols 0..256 with the stripe's byte counts, symbol 256 counted once; at most 15 bits.  Lengths
+ *     (the same rule gives the code-length code below, with limit 7):
+ *       a. Leaves: the symbols with a non-zero count in ascending (count, symbol).
+ *       b. The plain Huffman tree: repeatedly the two lightest nodes become the children of a new internal node; among equal weights a
+ *          leaf goes before an internal node, leaves in the order of (a), internal nodes in the order they were made.
+ *       c. n[l] = the number of leaves of depth l, depths beyond the limit counted at the limit (and a single leaf at depth 1).
+ *       d. While the Kraft sum of n exceeds 1 -- once per 2^-limit it is over: with l the longest length below the limit that has
+ *          n[l] > 0: n[l] -= 1, n[l + 1] += 2, n[limit] -= 1 (the step of zlib's gen_bitlen).
+ *       e. The lengths are handed out in the order of (a): the first n[limit] leaves get the limit, the next n[limit - 1] one less, ...
+ *     Codes: canonical, RFC 1951 3.2.2 (per length counting up in symbol order), packed from the most significant bit of the code as
+ *     RFC 1951 3.1.1 asks.  A stripe always has two symbols (a byte and 256), so a stripe of one byte value gets two codes of length 1.
+ *   The block header: BFINAL, BTYPE = 2, HLIT = 0 (257 codes: 256 is always in use), HDIST = 0 (ONE distance code, of length 1, never
+ *     used: RFC 1951 3.2.7), HCLEN = the least that covers the code-length symbols in use in the order 16 17 18 0 8 7 9 6 10 5 11 4 12
+ *     3 13 2 14 1 15 (at least 4), that many 3-bit lengths, then the 257 literal lengths and the distance length 1, each sent as
+ *     itself: the run-length symbols 16, 17 and 18 are never used.  The code-length code is built by (a)-(e) from how often each length
+ *     0..15 occurs among those 258, with limit 7.  A header is at most 17 + 19 * 3 + 258 * 7 = 1880 bits.
+ *   Size: a symbol is at most 15 bits, so with S stripes the stream is at most S * (1880 + 15) + 15 * H * (W C + 1) bits:
+ *     ideas_png_file_max_bytes = 43 + ceil(bits / 8) + 20; 0 for arguments the writer refuses (C other than 1 or 3, H or W <= 0, a
+ *     bound beyond 2^31 - 1).
+ * files: uint8 [B][row_stride], row_stride >= the bound; nbytes[b] = the length of file b, the bytes behind it unspecified (but inside
+ * the bound).  workspace: ideas_png_file_encode_workspace_bytes (0 for refused arguments or B * H beyond 2^31 - 1), any alignment, any
+ * contents: what needs zeros is cleared on the stream inside the call.  Nothing is written outside files, nbytes and workspace; no
+ * host synchronisation, no table copied from the host.  Bit and byte offsets inside an image are 64-bit.
+ * Four launches behind one memset: one workgroup a row filters it and adds its bytes to the stripe's histogram; one wave a stripe
+ * builds the codes, the header's bits and the stripe's bit count; one workgroup a stripe writes its block at its bit offset (a run's
+ * first and last 32-bit word, shared with its neighbours, by atomicOr: the result does not depend on the order); one workgroup an
+ * image computes Adler-32 and the CRCs from per-thread slices (a slice's CRC register times x^(8 * bytes behind it) modulo the
+ * polynomial), frames the chunks, copies the stream and writes the length.  Every grid is exact.  The result is bitwise reproducible.
+ * IDEAS_E_NULL: files, nbytes, u8 or workspace is NULL.  IDEAS_E_SHAPE: B, C, H or W <= 0, row_stride below the bound, a size the size
+ * queries answer with 0.  IDEAS_E_UNSUPPORTED: a positive C other than 1 or 3.  Every check comes before any launch.
+ * (Additive within ABI 4: IDEAS_ABI_VERSION stays 4.) */
+#ifndef IDEAS_PNG_STRIPE_ROWS
+#define IDEAS_PNG_STRIPE_ROWS 32
+#endif
+size_t ideas_png_file_max_bytes(int C, int H, int W);
+size_t ideas_png_file_encode_workspace_bytes(int B, int C, int H, int W);
+int ideas_png_file_encode(void* files, int* nbytes, long long row_stride, const void* u8, void* workspace, int B, int C, int H, int W,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The JPEG file, read, csrc/jpeg_decode.hip: from the entropy-coded segment of B baseline files to their quantised coefficients and
  * to the pixels libjpeg / libjpeg-turbo decodes -- Pillow's Image.open, to the byte.  tests/jpegdecode_ref.py restates it in Python
  * and tests/test_jpeg_decode.py holds that restatement to Pillow's own pixels.  The header of a file is read on the host
